@@ -1,6 +1,20 @@
 """Headline benchmark: 'attention' captioner training images/sec on MI355X.
 
-python bench.py --gpus N --steps K --warmup W
+python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes its outputs if ``--dump-outputs`` is given and
+prints the result line (``roofline`` and ``cpu_baseline`` are null in it). ``--full`` adds the
+measurements that take runs of their own after the timed region: the per-kernel roofline passes and the
+CPU baseline described below (``--no-roofline`` / ``--no-cpu-baseline`` drop one of them again).
+
+``--dump-outputs DIR`` writes what the last timed call of the step left with its caller as
+``DIR/<name>.npy`` (float32; float64 for fp64 tensors), taken right after the clock stops: ``loss``
+(the loss that call returned), ``features`` (the encoder output that call produced, where the step
+keeps it), and for every trainable tensor ``param.<name>`` (after the last update) and ``grad.<name>``
+(``enc_param.`` / ``enc_grad.`` for the fine-tuned encoder). A tensor above the per-array cap is
+written as a fixed sample (numpy default_rng(0) indices, sorted, of the flattened tensor), so the whole
+directory stays under 64 MB. Weights, batch and dropout seed are fixed, so two builds run with the same
+arguments can be compared array for array.
 
 N > 1: one rank per GPU over RCCL. Under torchrun (WORLD_SIZE set) the ranks are the launcher's;
 without it, this process starts ``python -m torch.distributed.run --nproc-per-node N`` on itself
@@ -26,7 +40,7 @@ calls run exactly K encoder passes and K decoder/optimizer passes: the pipeline 
 warm-up and drained after the clock stops). ``--sequential`` runs the whole step as one HIP
 graph instead.
 
-Rank 0 prints ONE JSON line. ``roofline`` is for the dominant kernel: the conv implicit-GEMM
+Rank 0 prints ONE JSON line. With ``--full``, ``roofline`` is for the dominant kernel: the conv implicit-GEMM
 instantiation with the most time per step (the conv family is 86% of the step's FLOPs; the
 family aggregate is reported beside it). achieved = that kernel's algorithmic conv FLOPs /
 its summed launch time. The launch times come from a timing pass right after the timed region:
@@ -36,7 +50,7 @@ rocprofv3 reports for that dispatch), encoder and decoder on one stream -- the c
 kernel trace runs the bench in (its tracing serializes the two streams), so the committed trace
 summary of the same command gives the same per-launch average. ``roofline.in_pipeline`` repeats the
 pass with the timed region's two-stream pipelining: the same kernel slowed by the decoder's kernels.
-``cpu_baseline`` times the CPU oracle (op-for-op restatement of the reference step) on the
+``cpu_baseline`` (``--full``) times the CPU oracle (op-for-op restatement of the reference step) on the
 host cores, rank 0 at N = 1 only: the full batch (64 images) for at least one step.
 
 ``--config baseline_cpu`` is BASELINE config 1 (the 'baseline' LSTM captioner at batch 4 on
@@ -72,7 +86,13 @@ def parse():
     ap.add_argument("--image-size", type=int, default=224)
     ap.add_argument("--caption-len", type=int, default=25)
     ap.add_argument("--vocab", type=int, default=8100)
-    ap.add_argument("--no-roofline", action="store_true", help="skip per-conv event timing")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the per-conv roofline timing passes and the CPU "
+                         "baseline (a plain run reports roofline / cpu_baseline as null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left with its caller (loss, features, updated "
+                         "parameters, gradients) as DIR/<name>.npy, sampled to stay under 64 MB in all")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip per-conv event timing")
     ap.add_argument("--sequential", action="store_true",
                     help="no encoder/decoder pipelining: the whole step in one HIP graph (or --eager)")
     ap.add_argument("--eager", action="store_true",
@@ -92,7 +112,7 @@ def parse():
                     help="decoder GEMM arithmetic (AttentionDecoder.set_compute_precision): auto = bf16 for the "
                          "bf16 config, else x3 (fp32-accurate three-term split on the bf16 matrix cores: 1.80 vs "
                          "1.92 ms of decoder GEMMs per step, +0.4 %% img/s); fp32 = v_mfma_f32_32x32x2_f32")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=20.0,
                     help="cpu_baseline: keep stepping the oracle at the full batch until this much time "
                          "has passed (at least one step)")
@@ -100,7 +120,46 @@ def parse():
     args = ap.parse_args()
     if args.batch is None:
         args.batch = 4 if args.config == "baseline_cpu" else 64
+    if not args.full:  # the roofline passes and the CPU baseline are runs of their own: --full only
+        args.no_roofline = args.no_cpu_baseline = True
     return args
+
+
+DUMP_BUDGET = 48 << 20   # bytes --dump-outputs may write over all arrays (the limit is 64 MB)
+DUMP_ARRAY_CAP = 1 << 18  # elements of one array before it is sampled
+
+
+def _dump_sample(x, cap):
+    """``x`` as a float32 (float64 for fp64) numpy array: whole if it has at most ``cap`` elements, else the
+    elements of the flattened tensor at default_rng(0)'s ``cap`` sorted indices (the same for every run)."""
+    x = x.detach()
+    x = x if x.dtype == torch.float64 else x.float()
+    if x.numel() > cap:
+        idx = np.sort(np.random.default_rng(0).choice(x.numel(), cap, replace=False))
+        x = x.reshape(-1)[torch.from_numpy(idx).to(x.device)]
+    return x.cpu().numpy().copy()
+
+
+def snapshot_outputs(tensors):
+    """{name: tensor} -> {name: numpy array} under DUMP_BUDGET in all (host copies, taken now)."""
+    tensors = {k: v for k, v in tensors.items() if v is not None}
+    cap = max(1, min(DUMP_ARRAY_CAP, DUMP_BUDGET // (8 * max(1, len(tensors)))))
+    return {k: _dump_sample(v, cap) for k, v in tensors.items()}
+
+
+def write_outputs(path, arrays):
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def _last_features(step):
+    """The encoder output of the step's last call where the step keeps it (pipelined modes), else None."""
+    if not getattr(step, "pipeline", False) or step._pend is None:
+        return None
+    if step._pend[0] == "graph":
+        return step._pend[1]["feats"]
+    return step._feats[step._pend[1]]
 
 
 def _free_port():
@@ -345,7 +404,7 @@ def run_baseline_cpu(args, ctx):
     for _ in range(args.steps):
         loss = one()
     cdist.barrier(ctx)
-    return time.perf_counter() - t0, float(loss.detach())
+    return time.perf_counter() - t0, float(loss.detach()), dec
 
 
 def timing_pass(args, make_step, imgs, caps, lens, timer, encoder, pipeline):
@@ -465,11 +524,22 @@ def main():
     timer.enabled = False
     rank_dts = cdist.gather_floats(dt_rank, ctx)
     dt = max(rank_dts)
+    dumped = None
+    if args.dump_outputs and ctx.rank == 0:
+        # the state the last timed call left: before the pipeline is drained (the drain is one more decoder pass)
+        outs = {"loss": loss.detach().reshape(1), "features": _last_features(step)}
+        for pre, mod in (("", decoder), ("enc_", encoder if ft else None)):
+            for n, q in (mod.named_parameters() if mod is not None else ()):
+                if q.requires_grad:
+                    outs[f"{pre}param.{n}"], outs[f"{pre}grad.{n}"] = q, q.grad
+        dumped = snapshot_outputs(outs)
     if pipe:  # K encoder and K decoder passes were timed; drain the in-flight encoder pass
         step.flush()
         torch.cuda.synchronize()
     loss_v = float(loss.item())
     K.sk_check()  # stream-K hand-off invariant over the timed run (raises if a hand-off timed out)
+    if dumped is not None:
+        write_outputs(args.dump_outputs, dumped)
     timing = None
     if not args.no_roofline:
         if args.eager:
@@ -574,8 +644,14 @@ def main():
 
 
 def main_baseline_cpu(args, ctx):
-    dt_rank, loss_v = run_baseline_cpu(args, ctx)
+    dt_rank, loss_v, dec = run_baseline_cpu(args, ctx)
     from capmi import dist as cdist
+    if args.dump_outputs and ctx.rank == 0:
+        outs = {"loss": torch.tensor([loss_v])}
+        for n, q in dec.named_parameters():
+            if q.requires_grad:
+                outs["param." + n], outs["grad." + n] = q, q.grad
+        write_outputs(args.dump_outputs, snapshot_outputs(outs))
     rank_dts = cdist.gather_floats(dt_rank, ctx)
     dt = max(rank_dts)
     N = ctx.world

@@ -45,6 +45,33 @@ def test_bench_single_rank():
     assert d["n_ranks"] == 1 and d["dist"]["world_size"] == 1
 
 
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """``--dump-outputs DIR`` writes the last timed step's loss, updated parameters and gradients as
+    float32 / float64 .npy files under 64 MB in all, identical from run to run (fixed inputs and weights);
+    ``--full`` is accepted and the plain line's keys are there."""
+    import numpy as np
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    lines = []
+    for d, extra in zip(dirs, ([], ["--full"])):
+        out = _run(["--gpus", "1", "--dump-outputs", str(d)] + extra)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines.append(_line(out))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in lines[0] and k in lines[1], k
+    assert lines[0]["steps"] == 2 and lines[0]["ms_per_step"] > 0
+    names = sorted(f.name for f in dirs[0].iterdir())
+    assert names == sorted(f.name for f in dirs[1].iterdir())
+    assert "loss.npy" in names and any(n.startswith("param.") for n in names) \
+        and any(n.startswith("grad.") for n in names) and all(n.endswith(".npy") for n in names)
+    assert sum(f.stat().st_size for f in dirs[0].iterdir()) <= 64 * 10 ** 6
+    for n in names:
+        a, b = np.load(dirs[0] / n), np.load(dirs[1] / n)
+        assert a.dtype in (np.float32, np.float64), (n, a.dtype)
+        assert np.isfinite(a).all(), n
+        assert np.array_equal(a, b), n
+    assert abs(float(np.load(dirs[0] / "loss.npy")[0]) - lines[0]["loss_last_step"]) <= 1e-5
+
+
 def test_bench_rejects_world_size_mismatch():
     """Under a launcher whose world size differs from --gpus the bench refuses to report."""
     out = _run(["--gpus", "2"], env={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})

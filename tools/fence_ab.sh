@@ -7,7 +7,8 @@ for v in ablibs/*.so; do
     echo "$v $(CAPMI_LIB=$PWD/$v timeout -k 10 60 python tools/gemm_one.py --shape $s --reps 100 2>&1 | grep TFLOP)" >> $out
   done
 done
+log=$(dirname $out)/fence_bench.log
 for v in ablibs/*.so ablibs/*.so; do
-  CAPMI_LIB=$PWD/$v timeout -k 10 150 python bench.py --steps 30 --warmup 3 --no-cpu-baseline > gpurun_out/fence_bench.log 2>&1
-  python -c "import json; d=json.loads([l for l in open('gpurun_out/fence_bench.log') if l.startswith('{')][-1]); r=d['roofline']; print('$v bench', d['value'], d['ms_per_step'], r['achieved'], r['conv_family']['conv_ms_per_step'])" >> $out
+  CAPMI_LIB=$PWD/$v timeout -k 10 150 python bench.py --steps 30 --warmup 3 --full --no-cpu-baseline > $log 2>&1
+  python -c "import json; d=json.loads([l for l in open('$log') if l.startswith('{')][-1]); r=d['roofline']; print('$v bench', d['value'], d['ms_per_step'], r['achieved'], r['conv_family']['conv_ms_per_step'])" >> $out
 done

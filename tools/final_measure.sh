@@ -6,10 +6,11 @@ R=$GRAFT_REPO_ROOT
 CFG=${CFG:-attention}
 P="cd /tmp && export TMPDIR=/tmp && rocprofv3"
 B="python $R/bench.py --config $CFG"
+F="$B --full"  # the line with the roofline passes (and the CPU baseline)
 O=$R/gpurun_out
 tools/gpu_steps.sh \
-  "400|bench_$CFG|$B > $O/bench_$CFG.json" \
-  "400|prof_$CFG|$P --kernel-trace --stats -d $O/prof_$CFG -o bench -- $B --no-cpu-baseline" \
+  "400|bench_$CFG|$F > $O/bench_$CFG.json" \
+  "400|prof_$CFG|$P --kernel-trace --stats -d $O/prof_$CFG -o bench -- $F --no-cpu-baseline" \
   "300|pmcf_$CFG|$P --pmc FETCH_SIZE -d $O/pmcf_$CFG -o pmc -- $B --no-cpu-baseline --steps 2 --warmup 1 --no-roofline" \
   "300|pmcw_$CFG|$P --pmc WRITE_SIZE -d $O/pmcw_$CFG -o pmc -- $B --no-cpu-baseline --steps 2 --warmup 1 --no-roofline" || exit $?
 python tools/prof_summary.py $O/prof_$CFG/bench_results.db --top 45 > $O/prof_$CFG.md && \

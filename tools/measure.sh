@@ -11,9 +11,10 @@ suite() {
   grep -q " passed" gpurun_out/suite.log && ! grep -q " failed" gpurun_out/suite.log
 }
 lines() {
-  tools/gpu_steps.sh "400|line_attention|python bench.py > gpurun_out/line_attention.json" \
-    "400|line_glove_finetune|python bench.py --config glove_finetune > gpurun_out/line_glove_finetune.json" \
-    "400|line_bert_attention|python bench.py --config bert_attention > gpurun_out/line_bert_attention.json"
+  L=${LINES_DIR:-$PWD/bench_lines}; mkdir -p "$L"  # the full lines (roofline, CPU baseline), one file per config
+  tools/gpu_steps.sh "400|line_attention|python bench.py --full > $L/line_attention.json" \
+    "400|line_glove_finetune|python bench.py --full --config glove_finetune > $L/line_glove_finetune.json" \
+    "400|line_bert_attention|python bench.py --full --config bert_attention > $L/line_bert_attention.json"
 }
 final() {
   for c in "$@"; do CFG=$c bash tools/final_measure.sh || return $?; done
