@@ -8,6 +8,10 @@ training forward (grouped h-GEMM, fused ReLU score, softmax + context + gate, LS
 ``enc_att(encoder_out)`` is computed once per image (the reference recomputes it every step,
 Q5). The selection logic (top-k over at most k*V scores, beam reordering) is a few tiny torch
 ops on the device, as in the reference.
+
+``BatchedBeamSearch`` runs the same algorithm for B images per call: the k beams of every image are
+rows of one batch of B*k, the features stay once per image, and selection and bookkeeping are HIP
+kernels (csrc/beam.hip), so a decode step is a fixed launch sequence without a host sync.
 """
 import torch
 
@@ -131,3 +135,152 @@ class BeamSearch:
             hh, ww = encoder_out.size(1), encoder_out.size(2)
             al = [[row[i * ww:(i + 1) * ww] for i in range(hh)] for row in al]
         return (done_seqs[best], al, True) + extra
+
+
+class BatchedBeamSearch(BeamSearch):
+    """Beam search over B images per call. The beams of image i are rows i*k .. i*k+k-1 of every per-step
+    tensor, its live ones compacted to the front. Features and ``enc_att`` features exist once per image
+    (``capmi_beam_att_fwd`` serves the k rows of an image from one load; nothing is expanded k-fold).
+    Selection and bookkeeping are two device entry points (``capmi_beam_select``, ``capmi_beam_advance``),
+    so a step needs no host sync: the host reads the device count of images that still have live beams
+    every ``sync_every`` steps only, and rebuilds the sequences after the loop from the back-pointers."""
+
+    def __init__(self, decoder, beam_size):
+        super().__init__(decoder, beam_size)
+        if self.k > 16:
+            raise ValueError("beam_size must be <= 16")
+        self.last_stats = None
+        self.last_live = None
+
+    @torch.no_grad()
+    def search(self, encoder_out, start_idx, end_idx, max_steps=50, return_all=False, return_alphas=True,
+               sync_every=8):
+        """encoder_out: (B, S, S, E) or (B, P, E). Returns a list of B tuples, each the single-image
+        method's: (sequence, alphas (steps+1, S, S) or (steps+1, P) nested lists, finished) [+ (finished
+        sequences, their scores) with ``return_all``]; failure: ([start, end], [], False). Without
+        ``return_alphas`` the alphas are []. ``last_stats`` = steps run and host syncs taken;
+        ``last_live`` = per image (sequences, scores) of the beams still live at the stop."""
+        if self.dec.use_bert:
+            raise NotImplementedError("beam search with BERT features (the reference notes it fails too)")
+        p = self._params()
+        dev = encoder_out.device
+        B, E = encoder_out.size(0), encoder_out.size(-1)
+        enc = encoder_out.reshape(B, -1, E).contiguous().float()
+        P, k = enc.size(1), self.k
+        R = B * k
+        A, D = p["W_ea"].shape[0], p["W_hh"].shape[1]
+        M, V = p["emb"].shape[1], p["W_fc"].shape[0]
+        X = M + E
+        T = int(max_steps) + 1
+        sync_every = max(1, int(sync_every))
+        f = dict(device=dev, dtype=torch.float32)
+        # per batch: att_enc and the initial state, once per image
+        att_enc = torch.empty(B * P, A, **f)
+        K.gemm(K.problem(B * P, A, E, enc, E, p["W_ea"], E, att_enc, A, bias=p["b_ea"]), AK, BW, K.TILE_64)
+        mean = torch.empty(B, E, **f)
+        K.mean_rows(enc, B, P, E, mean)
+        h0, c0 = torch.empty(B, D, **f), torch.empty(B, D, **f)
+        K.gemm([K.problem(B, D, E, mean, E, p["W_h"], E, h0, D, bias=p["b_h"]),
+                K.problem(B, D, E, mean, E, p["W_c"], E, c0, D, bias=p["b_c"])], AK, BW, K.TILE_64)
+        h = h0.repeat_interleave(k, 0).contiguous()
+        c = c0.repeat_interleave(k, 0).contiguous()
+        xin = torch.zeros(R, X, **f)
+        p_ad, p_gate = torch.empty(R, A, **f), torch.empty(R, E, **f)
+        p_hh, p_x = torch.empty(R, 4 * D, **f), torch.empty(R, 4 * D, **f)
+        e_ws = torch.empty(R, P, **f)
+        act, h2, c2 = torch.empty(R, 4 * D, **f), torch.empty(R, D, **f), torch.empty(R, D, **f)
+        logits = torch.empty(R, V, **f)
+        alphas = torch.zeros(T, R, P, **f) if return_alphas else None
+        cand_v = torch.empty(R * k, **f)
+        cand_w = torch.empty(R * k, dtype=torch.int32, device=dev)
+        prev = torch.full((R,), start_idx, dtype=torch.int64, device=dev)
+        # every small piece of beam state in one int32 buffer: one copy brings it to the host
+        sizes = dict(bp=T * 3 * R, fin_count=B, fin_step=R, fin_slot=R, fin_score=R, live=B, scores=R,
+                     images_live=1, parent=R, word=R, top=R)
+        state = torch.zeros(sum(sizes.values()), dtype=torch.int32, device=dev)
+        off, o = {}, 0
+        for name, n in sizes.items():
+            off[name] = (o, o + n)
+            o += n
+
+        def piece(buf, name, as_float=False):
+            v = buf[off[name][0]:off[name][1]]
+            return v.view(torch.float32) if as_float else v
+
+        bp = piece(state, "bp").view(T, 3, R)
+        live, images_live = piece(state, "live"), piece(state, "images_live")
+        live.fill_(k)
+        images_live.fill_(B)
+        scores, top = piece(state, "scores", True), piece(state, "top", True)
+        parent, word = piece(state, "parent"), piece(state, "word")
+        fin_count, fin_step, fin_slot = piece(state, "fin_count"), piece(state, "fin_step"), piece(state, "fin_slot")
+        fin_score = piece(state, "fin_score", True)
+
+        steps = syncs = 0
+        for t_ in range(T):
+            K.embed_gather(p["emb"], prev, R, 1, 1, xin, X)
+            K.gemm([K.problem(R, A, D, h, D, p["W_da"], D, p_ad, A),
+                    K.problem(R, E, D, h, D, p["W_fb"], D, p_gate, E),
+                    K.problem(R, 4 * D, D, h, D, p["W_hh"], D, p_hh, 4 * D)], AK, BW, K.TILE_64)
+            K.beam_att_fwd(enc, att_enc, p_ad, 1, 0, p["b_da"], p["wf"], p["bf"], p_gate, 1, 0, p["b_fb"], live,
+                           B, k, P, A, E, e_ws, alpha_out=alphas[t_] if return_alphas else None,
+                           x_out=xin[:, M:], ld_x=X)
+            K.gemm(K.problem(R, 4 * D, X, xin, X, p["W_ih"], X, p_x, 4 * D, bias=p["b_ih"], bias2=p["b_hh"]),
+                   AK, BW, K.TILE_64)
+            K.lstm_cell_fwd(p_x, 1, 0, None, p_hh, 1, 0, c, R, D, h2, c2, act)
+            K.gemm(K.problem(R, V, D, h2, D, p["W_fc"], D, logits, V, bias=p["b_fc"]), AK, BW, K.TILE_64)
+            K.beam_select(logits, scores, live, t_ == 0, B, k, V, cand_v, cand_w, parent, word, top)
+            K.beam_advance(parent, word, top, live, B, k, D, end_idx, t_, h2, c2, h, c, prev, scores,
+                           bp[t_, 0], bp[t_, 1], bp[t_, 2], fin_count, fin_step, fin_slot, fin_score, images_live)
+            steps += 1
+            if steps % sync_every == 0 and steps < T:
+                syncs += 1
+                if int(images_live.item()) == 0:
+                    break
+        host = state.cpu()
+        syncs += 1
+        bp_h = piece(host, "bp").view(T, 3, B, k).numpy()
+        live_h, nfin = piece(host, "live").tolist(), piece(host, "fin_count").tolist()
+        fstep, fslot = piece(host, "fin_step").view(B, k).tolist(), piece(host, "fin_slot").view(B, k).tolist()
+        fscore = piece(host, "fin_score", True).view(B, k).tolist()
+        scores_h = piece(host, "scores", True).view(B, k).tolist()
+
+        def walk(i, t_, slot):
+            """the beam selected at step t_ as slot: its words and, per step, the row whose alpha it took"""
+            words, rows = [], []
+            while True:
+                row = int(bp_h[t_, 0, i, slot])
+                words.append(int(bp_h[t_, 1, i, slot]))
+                rows.append(t_ * R + i * k + row)
+                if t_ == 0:
+                    break
+                t_ -= 1
+                slot = int(bp_h[t_, 2, i, row])
+            return [start_idx] + words[::-1], rows[::-1]
+
+        results, paths, self.last_live = [], [], []
+        for i in range(B):
+            done = [walk(i, fstep[i][q], fslot[i][q]) for q in range(nfin[i])]
+            dscores = fscore[i][:nfin[i]]
+            self.last_live.append(([walk(i, steps - 1, int(bp_h[steps - 1, 2, i, n]))[0] for n in range(live_h[i])],
+                                   scores_h[i][:live_h[i]]))
+            extra = (([d[0] for d in done], dscores),) if return_all else ()
+            if not done:
+                results.append(([start_idx, end_idx], [], False) + extra)
+                continue
+            best = dscores.index(max(dscores))
+            paths.append((i, len(results), done[best][1]))
+            results.append((done[best][0], [], True) + extra)
+        if return_alphas and paths:
+            idx = torch.tensor([r for _, _, rows in paths for r in rows], dtype=torch.int64).to(dev)
+            got = alphas.view(T * R, P).index_select(0, idx).cpu()
+            syncs += 1
+            o = 0
+            for i, slot, rows in paths:
+                al = torch.cat([torch.ones(1, P), got[o:o + len(rows)]], 0)
+                o += len(rows)
+                if encoder_out.dim() == 4:  # (steps+1, S, S) like the reference's seqs_alpha
+                    al = al.view(-1, encoder_out.size(1), encoder_out.size(2))
+                results[slot] = (results[slot][0], al.tolist(), True) + results[slot][3:]
+        self.last_stats = {"steps": steps, "host_syncs": syncs}
+        return results

@@ -622,6 +622,46 @@ def mask_rows_tb(x, bt_dev, T, B, cols, ld, r1=0, s2=0):
     call("capmi_mask_rows_tb", ptr(x), ptr(bt_dev), T, B, cols, ld, r1, s2, stream())
 
 
+# --------------------------------------------------------------------------------------
+# batched beam search (csrc/beam.hip): image i owns rows i*k .. i*k+k-1, live[i] of them in use
+# --------------------------------------------------------------------------------------
+def beam_att_fwd(enc, att_enc, dec_part, S_a, slab_a, bias_da, wf, bf, gate_part, S_g, slab_g, bias_fb, live,
+                 B, k, P, A, E, e_ws, alpha_out=None, awe_out=None, gate_out=None, x_out=None, ld_x=0):
+    """enc (B, P, E) and att_enc (B, P, A) once per image; dec_part / gate_part rows (B*k, .)."""
+    _cuda(enc, att_enc, dec_part, bias_da, wf, bf, gate_part, bias_fb, e_ws, alpha_out, awe_out, gate_out, x_out)
+    _cuda(live, dtype=torch.int32)
+    assert enc.is_contiguous() and att_enc.is_contiguous() and enc.numel() == B * P * E
+    assert att_enc.numel() == B * P * A and live.numel() >= B and e_ws.numel() >= B * k * P
+    call("capmi_beam_att_fwd", ptr(enc), ptr(att_enc), ptr(dec_part), S_a, slab_a, ptr(bias_da), ptr(wf), ptr(bf),
+         ptr(gate_part), S_g, slab_g, ptr(bias_fb), ptr(live), B, k, P, A, E, ptr(e_ws), ptr(alpha_out),
+         ptr(awe_out), ptr(gate_out), ptr(x_out), ld_x, stream())
+
+
+def beam_select(logits, scores, live, first_step, B, k, V, cand_v, cand_w, parent, word, top):
+    _cuda(logits, scores, cand_v, top)
+    _cuda(live, cand_w, parent, word, dtype=torch.int32)
+    assert logits.is_contiguous() and logits.numel() == B * k * V and scores.numel() >= B * k
+    assert cand_v.numel() >= B * k * k and cand_w.numel() >= B * k * k
+    assert min(parent.numel(), word.numel(), top.numel()) >= B * k and live.numel() >= B
+    call("capmi_beam_select", ptr(logits), ptr(scores), ptr(live), int(bool(first_step)), B, k, V, ptr(cand_v),
+         ptr(cand_w), ptr(parent), ptr(word), ptr(top), stream())
+
+
+def beam_advance(parent, word, top, live, B, k, D, end_idx, step, h_src, c_src, h_dst, c_dst, prev, scores,
+                 bp_parent, bp_word, bp_src, fin_count, fin_step, fin_slot, fin_score, images_live):
+    _cuda(top, h_src, c_src, h_dst, c_dst, scores, fin_score)
+    _cuda(parent, word, live, bp_parent, bp_word, bp_src, fin_count, fin_step, fin_slot, images_live,
+          dtype=torch.int32)
+    _cuda(prev, dtype=torch.int64)
+    n = B * k
+    assert min(x.numel() for x in (parent, word, top, prev, scores, bp_parent, bp_word, bp_src, fin_step,
+                                   fin_slot, fin_score)) >= n
+    assert min(x.numel() for x in (h_src, c_src, h_dst, c_dst)) >= n * D and min(live.numel(), fin_count.numel()) >= B
+    call("capmi_beam_advance", ptr(parent), ptr(word), ptr(top), ptr(live), B, k, D, int(end_idx), int(step),
+         ptr(h_src), ptr(c_src), ptr(h_dst), ptr(c_dst), ptr(prev), ptr(scores), ptr(bp_parent), ptr(bp_word),
+         ptr(bp_src), ptr(fin_count), ptr(fin_step), ptr(fin_slot), ptr(fin_score), ptr(images_live), stream())
+
+
 def ce_fwd_bwd(logits, caps, B, T, L, V, bt_dev, nrows, loss_rows, lse=None, dlogits=None,
                dl_time_major=False, gscale=None):
     _cuda(logits, loss_rows, lse, dlogits, gscale)

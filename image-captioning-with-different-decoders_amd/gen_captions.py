@@ -1,10 +1,11 @@
 """Caption generation with beam search (reference gen_captions.py:16-131), same function name and
 signature. On a HIP device the decode runs on capmi's kernels (capmi.beam.BeamSearch); the
 encoder is the capmi EncoderAttention. Image loading / plotting of the reference's CLI
-(imageio, matplotlib, checkpoints of whole modules) is outside the built path."""
+(imageio, matplotlib, checkpoints of whole modules) is outside the built path.
+``caption_images_beam_search`` is the batched form (capmi.beam.BatchedBeamSearch): B images per call."""
 import torch
 
-from capmi.beam import BeamSearch
+from capmi.beam import BatchedBeamSearch, BeamSearch
 from vocabulary import END_TOKEN, START_TOKEN
 
 
@@ -15,3 +16,14 @@ def attention_caption_image_beam_search(device, args, img, encoder, decoder, voc
     with torch.no_grad():
         encoder_out = encoder(img)  # (1, 14, 14, 2048)
     return BeamSearch(decoder, args.beam_size).search(encoder_out, vocab(START_TOKEN), vocab(END_TOKEN))
+
+
+def caption_images_beam_search(device, args, imgs, encoder, decoder, vocab):
+    """Captions a batch of images (B, 3, H, W) with beam search: one encoder forward for the batch, then
+    the batched beam search with its beam state on the device.
+
+    Returns a list of B tuples (caption token ids, attention weights (steps+1, 14, 14), finished), each
+    what ``attention_caption_image_beam_search`` returns for that image alone."""
+    with torch.no_grad():
+        encoder_out = encoder(imgs)  # (B, 14, 14, 2048)
+    return BatchedBeamSearch(decoder, args.beam_size).search(encoder_out, vocab(START_TOKEN), vocab(END_TOKEN))

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define CAPMI_ABI_VERSION 26
+#define CAPMI_ABI_VERSION 27
 
 #define CAPMI_OK 0
 #define CAPMI_EINVAL 1001   /* bad shape / argument */
@@ -520,6 +520,42 @@ int capmi_att_bwd_fused(const float* dx, int S, long long slab, const float* gat
                         float* dawe_out, const float* enc, const float* alpha, long long alpha_ld_b,
                         const float* dreg, long long dreg_ld_b, const float* att_enc, const float* att_dec,
                         const float* wf, int B, int P, int A, int E, int bt, float* de, float* dad, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Batched beam search (ABI 27, beam.hip; gen_captions.py:16-131 for B images at once).
+ * Row layout of all three: image i owns rows i*k .. i*k+k-1 (1 <= k <= 16); its live[i] (int32, 0..k)
+ * surviving beams sit in the first live[i] of them, in selection order. Rows at or past live[i] are
+ * dead: never read as candidates, and no output of theirs is written.
+ * ---------------------------------------------------------------------- */
+/* Soft attention + f_beta gate of every live row over features stored once per image: enc [B][P][E],
+ * att_enc [B][P][A]; dec_part / gate_part [B*k][A] / [B*k][E] as capmi_att_score_fwd /
+ * capmi_att_softmax_ctx_fwd take them (S slabs + bias; a final tensor is S = 1 with a NULL bias_da;
+ * gate_part == NULL: no gate). Writes alpha_out [B*k][P], awe_out [B*k][E], gate_out [B*k][E] and
+ * gate*awe to x_out[row*ld_x + e] (each optional). e_ws: [B*k][P] scratch for the scores. The rows of an
+ * image are served by the same workgroups, so each att_enc / enc element is loaded once for all of them. */
+int capmi_beam_att_fwd(const float* enc, const float* att_enc, const float* dec_part, int S_a,
+                       long long slab_a, const float* bias_da, const float* wf, const float* bf,
+                       const float* gate_part, int S_g, long long slab_g, const float* bias_fb,
+                       const int* live, int B, int k, int P, int A, int E, float* e_ws,
+                       float* alpha_out, float* awe_out, float* gate_out, float* x_out,
+                       long long ld_x, void* stream);
+/* Per image the best s = live[i] of the candidates scores[row j] + log_softmax(logits[row j])[w], j < s
+ * (first_step: row 0 only), descending, ties to the lower flat index j*V + w: parent / word / top
+ * [B][k], entries 0..s-1. logits [B*k][V], V >= k. cand_v / cand_w: [B*k][k] scratch. */
+int capmi_beam_select(const float* logits, const float* scores, const int* live, int first_step,
+                      int B, int k, int V, float* cand_v, int* cand_w, int* parent, int* word,
+                      float* top, void* stream);
+/* One step's bookkeeping in one launch. Selection slot r < live[i] with word == end_idx is appended
+ * to the image's finished list (fin_step / fin_slot / fin_score [B][k] at fin_count[i]++); the others
+ * are compacted in order into rows n = 0..: h_dst / c_dst [row n] = h_src / c_src [row parent[r]]
+ * ([B*k][D], src != dst), prev[row n] = word, scores[row n] = top, bp_src[i][n] = r. bp_parent /
+ * bp_word [B][k] (this step's slice) record the selection by slot. live[i] becomes the survivor
+ * count; *images_live is decremented when it reaches 0. */
+int capmi_beam_advance(const int* parent, const int* word, const float* top, int* live, int B, int k,
+                       int D, int end_idx, int step, const float* h_src, const float* c_src,
+                       float* h_dst, float* c_dst, long long* prev, float* scores, int* bp_parent,
+                       int* bp_word, int* bp_src, int* fin_count, int* fin_step, int* fin_slot,
+                       float* fin_score, int* images_live, void* stream);
 
 /* ------------------------------------------------------------------------
  * Optimiser (train_utils.py:2-12 clamp + torch.optim.Adam, models/attention.py:352-355,423-430)
