@@ -147,6 +147,9 @@ _SIGS = {
     "capmi_beam_select": [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "capmi_beam_advance": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp,
                            c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "capmi_eval_rows": [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "capmi_eval_captions": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_float, c_vp, c_vp, c_vp, c_vp, c_vp,
+                            c_vp],
     "capmi_adam_clamp": [c_vp, c_vp, c_vp, c_vp, c_ll, c_double, c_double, c_double, c_double, c_double,
                          c_double, c_double, c_vp, c_vp],
     "capmi_adam_clamp_f64": [c_vp, c_vp, c_vp, c_vp, c_ll, c_double, c_double, c_double, c_double,
@@ -188,7 +191,10 @@ def _load(path=LIB_PATH):
             "compute path; there is no fallback)")
     lib = ctypes.CDLL(path)
     for name, args in _SIGS.items():
-        fn = getattr(lib, name)
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:  # entry points are added without an ABI bump: a stale build lacks them
+            raise ImportError(f"libcapmi.so at {path} has no {name}; rebuild it") from None
         fn.argtypes = args
         fn.restype = _RESTYPES.get(name, c_int)
     if lib.capmi_abi_version() != ABI_VERSION:

@@ -662,6 +662,32 @@ def beam_advance(parent, word, top, live, B, k, D, end_idx, step, h_src, c_src, 
          ptr(bp_src), ptr(fin_count), ptr(fin_step), ptr(fin_slot), ptr(fin_score), ptr(images_live), stream())
 
 
+# --------------------------------------------------------------------------------------
+# teacher-forced validation (csrc/eval.hip): lens[b] = caption b's own decode length, any order
+# --------------------------------------------------------------------------------------
+def eval_rows(logits, caps, B, T, L, V, lens, loss_rows, pred, rank=None):
+    """Per row r = b*T + t of the (B, T, V) logits: loss_rows, greedy token ``pred`` and the target's ``rank``."""
+    _cuda(logits, loss_rows)
+    _cuda(caps, dtype=torch.int64)
+    _cuda(lens, pred, rank, dtype=torch.int32)
+    assert logits.is_contiguous() and logits.numel() == B * T * V and caps.is_contiguous()
+    assert caps.numel() == B * L and (lens is None or lens.numel() >= B)
+    assert min(x.numel() for x in (loss_rows, pred) + (() if rank is None else (rank,))) >= B * T
+    call("capmi_eval_rows", ptr(logits), ptr(caps), B, T, L, V, ptr(lens), ptr(loss_rows), ptr(pred), ptr(rank),
+         stream())
+
+
+def eval_captions(loss_rows, rank, alphas, lens, B, T, P, alpha_c, cap_ce, cap_reg, cap_loss, cap_top1, cap_top5):
+    """Per caption: CE mean over its rows, regulariser over the (B, T, P) alphas' first lens[b] steps, top-1/5."""
+    _cuda(loss_rows, alphas, cap_ce, cap_reg, cap_loss)
+    _cuda(rank, lens, cap_top1, cap_top5, dtype=torch.int32)
+    assert alphas.is_contiguous() and alphas.numel() == B * T * P and (lens is None or lens.numel() >= B)
+    assert min(loss_rows.numel(), rank.numel()) >= B * T
+    assert min(x.numel() for x in (cap_ce, cap_reg, cap_loss, cap_top1, cap_top5)) >= B
+    call("capmi_eval_captions", ptr(loss_rows), ptr(rank), ptr(alphas), ptr(lens), B, T, P, float(alpha_c),
+         ptr(cap_ce), ptr(cap_reg), ptr(cap_loss), ptr(cap_top1), ptr(cap_top5), stream())
+
+
 def ce_fwd_bwd(logits, caps, B, T, L, V, bt_dev, nrows, loss_rows, lse=None, dlogits=None,
                dl_time_major=False, gscale=None):
     _cuda(logits, loss_rows, lse, dlogits, gscale)

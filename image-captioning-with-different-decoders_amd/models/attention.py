@@ -357,4 +357,88 @@ def evaluate(device, args, encoder, decoder, val_loader=None):
     return metrics
 
 
-__all__ = ["SoftAttention", "AttentionDecoderParams", "AttentionDecoder", "train", "evaluate"]
+def evaluate_batched(device, args, encoder, decoder, dataset=None, batch_size=64):
+    """The validation pass of ``evaluate`` over ``batch_size`` captions per step, with per-caption
+    results equal to what the reference computes one caption at a time (reference :454-567 at batch 1).
+
+    ``dataset``: items ``(img, caption)`` or the val-mode 4-tuple; default the reference's COCO 'val' set
+    (needs the dataset). Captions are taken in dataset order (no shuffle), padded to the batch maximum and
+    passed with their true lengths. Per batch: one encoder forward, capmi.evalpass.TeacherForcedEval (loss,
+    greedy tokens and top-1 / top-5 counts on the device), one asynchronous copy of the small result buffer
+    to pinned host memory; the device is synchronised only every ``print_freq`` batches and at the end.
+
+    Returns a JSON-serialisable dict: the capmi.scoring.caption_scores keys (BLEU-1..4, ROUGE-L, CIDEr; no
+    METEOR), ``losses`` (per caption, dataset order), ``loss`` (their average weighted by decode length:
+    the running figure of the reference's log line), ``top1_acc`` / ``top5_acc`` over all scored rows,
+    ``references`` and ``hypotheses`` (built as the reference builds them at batch 1: the START/END/PAD-
+    stripped target repeated once per target position of that caption, and the stripped greedy tokens)."""
+    from torch.nn.utils.rnn import pad_sequence
+    from capmi import evalpass
+    from capmi.scoring import caption_scores
+    from vocabulary import END_TOKEN, START_TOKEN
+    if dataset is None:
+        from dataset import COCODataset  # real COCO path (pycocotools, nltk, images)
+        dataset = COCODataset(mode='val', caption_max_len=args.max_caption_length)
+    vocab = decoder.vocab
+    pad_idx = vocab(PAD_TOKEN)
+    drop = {vocab(START_TOKEN), vocab(END_TOKEN), pad_idx}
+
+    def collate_fn(data):
+        imgs, captions = list(zip(*data))[:2]
+        return (torch.stack(imgs, dim=0), pad_sequence(captions, batch_first=True, padding_value=pad_idx),
+                [len(c) for c in captions])  # true lengths (evaluate's loader pads first: equal at batch 1)
+
+    loader = torch.utils.data.DataLoader(dataset=dataset, batch_size=int(batch_size), shuffle=False,
+                                         num_workers=int(getattr(args, "workers", 0) or 0), collate_fn=collate_fn)
+    on_gpu = torch.device(device).type == "cuda"
+    tf_eval = evalpass.TeacherForcedEval(decoder, alpha_c=1.0)  # the reference's validation loss: (1 - sum alpha)^2
+    evaluate_batched.last_eval = tf_eval  # (tests: its last_stats)
+    references, hypotheses, losses = [], [], []
+    hits1 = hits5 = rows = 0
+    accum_loss = AccumulatingMetric()
+    decoder.eval()
+    encoder.eval()
+    num_batches = len(loader)
+    start_time = time.time()
+    pending = []
+
+    def drain():
+        nonlocal hits1, hits5, rows
+        if on_gpu:
+            torch.cuda.synchronize()
+        for host, caps_h, lengths, T in pending:
+            res = evalpass.unpack(host, len(lengths), T)
+            loss_h, pred_h = res["cap_loss"].tolist(), res["pred"].tolist()
+            hits1 += int(res["top1"].sum())
+            hits5 += int(res["top5"].sum())
+            for i, n in enumerate(lengths):
+                dl = n - 1
+                accum_loss.update(loss_h[i], dl)
+                losses.append(loss_h[i])
+                rows += dl
+                ref = [w for w in caps_h[i][1:n] if w not in drop]
+                references.append([ref for _ in range(dl)])  # reference :527-528, at this caption's own length
+                hypotheses.append([w for w in pred_h[i][:dl] if w not in drop])
+        del pending[:]
+
+    with torch.no_grad():
+        for batch_idx, (imgs, captions, caption_lengths) in enumerate(loader):
+            imgs = imgs.to(device, non_blocking=True)
+            res = tf_eval(encoder(imgs), captions.to(device, non_blocking=True), caption_lengths)
+            packed = res["packed"]
+            host = torch.empty(packed.shape, dtype=packed.dtype, pin_memory=on_gpu)
+            host.copy_(packed, non_blocking=True)
+            pending.append((host, captions.tolist(), caption_lengths, res["pred"].shape[1]))
+            if batch_idx % args.print_freq == 0:
+                drain()
+                print(f'Batch {batch_idx+1}/{num_batches}, Loss {accum_loss.avg():.4f}')
+        drain()
+    metrics = caption_scores(references, hypotheses)
+    metrics.update(losses=losses, loss=accum_loss.avg(), top1_acc=hits1 / max(rows, 1), top5_acc=hits5 / max(rows, 1),
+                   references=references, hypotheses=hypotheses)
+    print(f'Checkpoint {getattr(args, "checkpoint", None)} finished evaluation in '
+          f'{time.time() - start_time:.4f} seconds.')
+    return metrics
+
+
+__all__ = ["SoftAttention", "AttentionDecoderParams", "AttentionDecoder", "train", "evaluate", "evaluate_batched"]

@@ -8,3 +8,4 @@ class PathConfig:
     val_anno_file = 'cocoapi/annotations/captions_val2014.json'
     train_img_dir = 'cocoapi/images/train2014'
     val_img_dir = 'cocoapi/images/val2014'
+    eval_data = 'eval_data'

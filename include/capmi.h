@@ -558,6 +558,26 @@ int capmi_beam_advance(const int* parent, const int* word, const float* top, int
                        float* fin_score, int* images_live, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Teacher-forced validation (models/attention.py:454-567 for B captions at once; csrc/eval.hip).
+ * Added under ABI 27: new symbols only, nothing existing changed.
+ * ---------------------------------------------------------------------- */
+/* One workgroup per row r = b*T + t of logits (B,T,V), one pass over the row. lens[b] (clamped to
+ * [0, T]; NULL: T) is caption b's own decode length, so captions come in any order. Active row
+ * (t < lens[b]), tgt = caps[b*L + t + 1] (L > T): loss_rows[r] = logsumexp(x) - x[tgt]; pred[r] = the
+ * smallest index attaining max(x); rank[r] (optional) = #{v : x[v] > x[tgt]} + #{v < tgt : x[v] ==
+ * x[tgt]}, the target's 0-based place in a stable descending sort. tgt outside [0, V): nothing is read
+ * for it, loss_rows[r] = +inf, rank[r] = V. Inactive row: loss_rows[r] = 0, pred[r] = rank[r] = -1. */
+int capmi_eval_rows(const float* logits, const long long* caps, int B, int T, int L, int V,
+                    const int* lens, float* loss_rows, int* pred, int* rank, void* stream);
+/* One workgroup per caption, fixed reduction order. n = lens[b] clamped to [0, T] (NULL: T):
+ * cap_ce[b] = sum_{t<n} loss_rows[b*T+t] / n; cap_reg[b] = sum_p (alpha_c - sum_{t<n} alphas[b][t][p])^2 / P
+ * (alphas (B,T,P); rows t >= n are never read); cap_loss = cap_ce + cap_reg; cap_top1[b] = #{t<n : rank == 0};
+ * cap_top5[b] = #{t<n : 0 <= rank < 5}. n == 0: all five are 0. Every pointer but lens is required. */
+int capmi_eval_captions(const float* loss_rows, const int* rank, const float* alphas, const int* lens,
+                        int B, int T, int P, float alpha_c, float* cap_ce, float* cap_reg,
+                        float* cap_loss, int* cap_top1, int* cap_top5, void* stream);
+
+/* ------------------------------------------------------------------------
  * Optimiser (train_utils.py:2-12 clamp + torch.optim.Adam, models/attention.py:352-355,423-430)
  * p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps) with g clamped to +-clip first.
  * step_dev == NULL: bc1 = 1 - beta1^t and bc2_sqrt = sqrt(1 - beta2^t) as passed (host step t);
