@@ -150,6 +150,10 @@ _SIGS = {
     "capmi_eval_rows": [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
     "capmi_eval_captions": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_float, c_vp, c_vp, c_vp, c_vp, c_vp,
                             c_vp],
+    "capmi_lstm_step_fwd": [c_vp, c_ll, c_vp, c_ll, c_int, c_vp, c_ll, c_vp, c_ll, c_vp, c_vp, c_vp, c_vp, c_int,
+                            c_int, c_vp, c_vp, c_vp],
+    "capmi_eval_rows_at": [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "capmi_eval_captions_ce": [c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp],
     "capmi_adam_clamp": [c_vp, c_vp, c_vp, c_vp, c_ll, c_double, c_double, c_double, c_double, c_double,
                          c_double, c_double, c_vp, c_vp],
     "capmi_adam_clamp_f64": [c_vp, c_vp, c_vp, c_vp, c_ll, c_double, c_double, c_double, c_double,

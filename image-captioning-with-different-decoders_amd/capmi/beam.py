@@ -12,6 +12,9 @@ ops on the device, as in the reference.
 ``BatchedBeamSearch`` runs the same algorithm for B images per call: the k beams of every image are
 rows of one batch of B*k, the features stay once per image, and selection and bookkeeping are HIP
 kernels (csrc/beam.hip), so a decode step is a fixed launch sequence without a host sync.
+
+``BaselineBatchedBeamSearch`` is the same search for the baseline (LSTM) captioner: the step is one
+capmi_lstm_step_fwd launch (csrc/baseline_step.hip), selection and bookkeeping are the same two kernels.
 """
 import torch
 
@@ -282,5 +285,128 @@ class BatchedBeamSearch(BeamSearch):
                 if encoder_out.dim() == 4:  # (steps+1, S, S) like the reference's seqs_alpha
                     al = al.view(-1, encoder_out.size(1), encoder_out.size(2))
                 results[slot] = (results[slot][0], al.tolist(), True) + results[slot][3:]
+        self.last_stats = {"steps": steps, "host_syncs": syncs}
+        return results
+
+
+class BaselineBatchedBeamSearch:
+    """Beam search of the baseline (LSTM) captioner over B images per call (the reference has none: the
+    semantics are ``attention_caption_image_beam_search``'s with the baseline recurrence). The state after
+    feeding the image feature to the LSTM from a zero state is the initial (h, c) of all k beams of an image
+    (that step's output, which predicts START in training, is discarded); sequences start as [START] with
+    score 0; a step is h, c = LSTM(embedding(prev), (h, c)), logits = linear(h), then the selection and
+    bookkeeping of ``BatchedBeamSearch`` on the same two device entry points. Rows i*k .. i*k+k-1 belong to
+    image i. Per step: embed_gather, capmi_lstm_step_fwd, the R x V x H GEMM, capmi_beam_select,
+    capmi_beam_advance; no host sync but the ``sync_every`` read of the count of images still live."""
+
+    def __init__(self, decoder, beam_size):
+        self.dec = decoder
+        self.k = int(beam_size)
+        if self.k < 1:
+            raise ValueError("beam_size must be >= 1")
+        if self.k > 16:
+            raise ValueError("beam_size must be <= 16")
+        self.last_stats = None
+        self.last_live = None
+
+    @torch.no_grad()
+    def search(self, img_features, start_idx, end_idx, max_steps=50, return_all=False, sync_every=8):
+        """img_features (B, M): the encoder's output. Returns a list of B tuples (sequence, [], finished) [+
+        (finished sequences, their scores) with ``return_all``]; failure: ([start, end], [], False).
+        ``last_stats`` = steps run and host syncs taken; ``last_live`` = per image (sequences, scores) of the
+        beams still live at the stop."""
+        from .baseline_eval import STEP_FUSED, lstm_step
+        dec = self.dec
+        if not img_features.is_cuda:
+            raise RuntimeError("capmi baseline decoder path needs HIP tensors")
+        dev = img_features.device
+        feats = img_features.contiguous().float()
+        B, k = feats.size(0), self.k
+        R = B * k
+        M, D = dec.embed_size, dec.hidden_size
+        emb, w_lin, b_lin = dec.embedding.weight, dec.linear.weight, dec.linear.bias
+        V = w_lin.shape[0]
+        if feats.dim() != 2 or feats.size(1) != M:
+            raise ValueError(f"img_features must be (B, {M})")
+        T = int(max_steps) + 1
+        sync_every = max(1, int(sync_every))
+        f = dict(device=dev, dtype=torch.float32)
+        scratch = None if STEP_FUSED else torch.empty(4, R, 4 * D, **f)
+        h0, c0 = torch.empty(B, D, **f), torch.empty(B, D, **f)
+        lstm_step(dec, B, h0, c0, x=feats, ld_x=M, scratch=scratch)
+        h = h0.repeat_interleave(k, 0).contiguous()
+        c = c0.repeat_interleave(k, 0).contiguous()
+        xin = torch.empty(R, M, **f)
+        h2, c2 = torch.empty(R, D, **f), torch.empty(R, D, **f)
+        logits = torch.empty(R, V, **f)
+        cand_v = torch.empty(R * k, **f)
+        cand_w = torch.empty(R * k, dtype=torch.int32, device=dev)
+        prev = torch.full((R,), start_idx, dtype=torch.int64, device=dev)
+        # every small piece of beam state in one int32 buffer: one copy brings it to the host
+        sizes = dict(bp=T * 3 * R, fin_count=B, fin_step=R, fin_slot=R, fin_score=R, live=B, scores=R,
+                     images_live=1, parent=R, word=R, top=R)
+        state = torch.zeros(sum(sizes.values()), dtype=torch.int32, device=dev)
+        off, o = {}, 0
+        for name, n in sizes.items():
+            off[name] = (o, o + n)
+            o += n
+
+        def piece(buf, name, as_float=False):
+            v = buf[off[name][0]:off[name][1]]
+            return v.view(torch.float32) if as_float else v
+
+        bp = piece(state, "bp").view(T, 3, R)
+        live, images_live = piece(state, "live"), piece(state, "images_live")
+        live.fill_(k)
+        images_live.fill_(B)
+        scores, top = piece(state, "scores", True), piece(state, "top", True)
+        parent, word = piece(state, "parent"), piece(state, "word")
+        fin_count, fin_step, fin_slot = piece(state, "fin_count"), piece(state, "fin_step"), piece(state, "fin_slot")
+        fin_score = piece(state, "fin_score", True)
+
+        steps = syncs = 0
+        for t_ in range(T):
+            K.embed_gather(emb, prev, R, 1, 1, xin, M)
+            lstm_step(dec, R, h2, c2, x=xin, ld_x=M, h_prev=h, c_prev=c, scratch=scratch)
+            K.gemm(K.problem(R, V, D, h2, D, w_lin, D, logits, V, bias=b_lin), AK, BW, K.TILE_64)
+            K.beam_select(logits, scores, live, t_ == 0, B, k, V, cand_v, cand_w, parent, word, top)
+            K.beam_advance(parent, word, top, live, B, k, D, end_idx, t_, h2, c2, h, c, prev, scores,
+                           bp[t_, 0], bp[t_, 1], bp[t_, 2], fin_count, fin_step, fin_slot, fin_score, images_live)
+            steps += 1
+            if steps % sync_every == 0 and steps < T:
+                syncs += 1
+                if int(images_live.item()) == 0:
+                    break
+        host = state.cpu()
+        syncs += 1
+        bp_h = piece(host, "bp").view(T, 3, B, k).numpy()
+        live_h, nfin = piece(host, "live").tolist(), piece(host, "fin_count").tolist()
+        fstep, fslot = piece(host, "fin_step").view(B, k).tolist(), piece(host, "fin_slot").view(B, k).tolist()
+        fscore = piece(host, "fin_score", True).view(B, k).tolist()
+        scores_h = piece(host, "scores", True).view(B, k).tolist()
+
+        def walk(i, t_, slot):
+            """the words of the beam selected at step t_ as slot, back through the back-pointers"""
+            words = []
+            while True:
+                row = int(bp_h[t_, 0, i, slot])
+                words.append(int(bp_h[t_, 1, i, slot]))
+                if t_ == 0:
+                    break
+                t_ -= 1
+                slot = int(bp_h[t_, 2, i, row])
+            return [start_idx] + words[::-1]
+
+        results, self.last_live = [], []
+        for i in range(B):
+            done = [walk(i, fstep[i][q], fslot[i][q]) for q in range(nfin[i])]
+            dscores = fscore[i][:nfin[i]]
+            self.last_live.append(([walk(i, steps - 1, int(bp_h[steps - 1, 2, i, n])) for n in range(live_h[i])],
+                                   scores_h[i][:live_h[i]]))
+            extra = ((done, dscores),) if return_all else ()
+            if not done:
+                results.append(([start_idx, end_idx], [], False) + extra)
+                continue
+            results.append((done[dscores.index(max(dscores))], [], True) + extra)
         self.last_stats = {"steps": steps, "host_syncs": syncs}
         return results

@@ -688,6 +688,45 @@ def eval_captions(loss_rows, rank, alphas, lens, B, T, P, alpha_c, cap_ce, cap_r
          ptr(cap_ce), ptr(cap_reg), ptr(cap_loss), ptr(cap_top1), ptr(cap_top5), stream())
 
 
+def eval_rows_at(logits, caps, B, T, L, V, tgt_off, lens, loss_rows, pred, rank=None):
+    """``eval_rows`` with the target of row (b, t) at ``caps[b, t + tgt_off]`` (the baseline model: 0)."""
+    _cuda(logits, loss_rows)
+    _cuda(caps, dtype=torch.int64)
+    _cuda(lens, pred, rank, dtype=torch.int32)
+    assert logits.is_contiguous() and logits.numel() == B * T * V and caps.is_contiguous()
+    assert caps.numel() == B * L and (lens is None or lens.numel() >= B)
+    assert min(x.numel() for x in (loss_rows, pred) + (() if rank is None else (rank,))) >= B * T
+    call("capmi_eval_rows_at", ptr(logits), ptr(caps), B, T, L, V, int(tgt_off), ptr(lens), ptr(loss_rows),
+         ptr(pred), ptr(rank), stream())
+
+
+def eval_captions_ce(loss_rows, rank, lens, B, T, cap_ce, cap_top1, cap_top5):
+    """Per caption: CE mean over its first lens[b] rows and the top-1/5 counts (no regulariser)."""
+    _cuda(loss_rows, cap_ce)
+    _cuda(rank, lens, cap_top1, cap_top5, dtype=torch.int32)
+    assert min(loss_rows.numel(), rank.numel()) >= B * T and (lens is None or lens.numel() >= B)
+    assert min(x.numel() for x in (cap_ce, cap_top1, cap_top5)) >= B
+    call("capmi_eval_captions_ce", ptr(loss_rows), ptr(rank), ptr(lens), B, T, ptr(cap_ce), ptr(cap_top1),
+         ptr(cap_top5), stream())
+
+
+# --------------------------------------------------------------------------------------
+# baseline (LSTM) captioner at inference (csrc/baseline_step.hip)
+# --------------------------------------------------------------------------------------
+def lstm_step_fwd(R, M, H, h_out, c_out, *, pre=None, ld_pre=0, x=None, ld_x=0, h_prev=None, ld_h=0, c_prev=None,
+                  ld_c=0, w_ih=None, w_hh=None, b_ih=None, b_hh=None):
+    """One LSTM timestep over R rows in one launch: gates = pre + x W_ih^T + h_prev W_hh^T + b_ih + b_hh (each
+    optional), then the cell; writes h_out / c_out (R, H) only. Leading dimensions default to the dense ones."""
+    _cuda(pre, x, h_prev, c_prev, w_ih, w_hh, b_ih, b_hh, h_out, c_out)
+    assert h_out.is_contiguous() and c_out.is_contiguous() and min(h_out.numel(), c_out.numel()) >= R * H
+    assert (w_ih is None or (w_ih.is_contiguous() and w_ih.numel() == 4 * H * M))
+    assert (w_hh is None or (w_hh.is_contiguous() and w_hh.numel() == 4 * H * H))
+    assert all(b is None or b.numel() == 4 * H for b in (b_ih, b_hh))
+    call("capmi_lstm_step_fwd", ptr(pre), int(ld_pre or 4 * H), ptr(x), int(ld_x or M), int(M), ptr(h_prev),
+         int(ld_h or H), ptr(c_prev), int(ld_c or H), ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh), int(R), int(H),
+         ptr(h_out), ptr(c_out), stream())
+
+
 def ce_fwd_bwd(logits, caps, B, T, L, V, bt_dev, nrows, loss_rows, lse=None, dlogits=None,
                dl_time_major=False, gscale=None):
     _cuda(logits, loss_rows, lse, dlogits, gscale)

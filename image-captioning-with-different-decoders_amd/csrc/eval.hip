@@ -5,6 +5,8 @@
 //   capmi_eval_rows     : one workgroup per row r = b*T + t; online max/sum as ce_fwd_bwd_kernel, with the
 //                         (value, index) arg-max and the target's rank carried through the same loop
 //   capmi_eval_captions : one workgroup per caption, sums in a fixed order (bit-identical run to run)
+//   capmi_eval_rows_at / capmi_eval_captions_ce : the same two for the baseline model's loss (reference
+//                         models/baseline.py:267-374): target column t + tgt_off (there 0), no regulariser
 //
 // lens[b] is the caption's own decode length, not a per-step prefix count: captions come in any order.
 #include <limits.h>
@@ -45,7 +47,7 @@ __device__ __forceinline__ bool eval_before(float v, int i, float ov, int oi) {
 // columns in ascending order, so a strict '>' keeps the lowest index of its own maximum.
 template <bool VEC>
 __global__ void __launch_bounds__(EVAL_T) eval_rows_kernel(
-    const float* __restrict__ logits, const long long* __restrict__ caps, int T, int L, int V,
+    const float* __restrict__ logits, const long long* __restrict__ caps, int T, int L, int V, int tgt_off,
     const int* __restrict__ lens, float* __restrict__ loss_rows, int* __restrict__ pred,
     int* __restrict__ rank) {
   __shared__ float red[16];
@@ -63,7 +65,7 @@ __global__ void __launch_bounds__(EVAL_T) eval_rows_kernel(
     return;
   }
   const float* x = logits + (long long)r * V;
-  const long long tgt = caps[(long long)b * L + t + 1];
+  const long long tgt = caps[(long long)b * L + t + tgt_off];
   const bool in_range = tgt >= 0 && tgt < V;
   const int itgt = in_range ? (int)tgt : 0;
   const float xt = in_range ? x[itgt] : INFINITY;  // every thread the same address: one broadcast load
@@ -127,19 +129,35 @@ __global__ void __launch_bounds__(EVAL_T) eval_rows_kernel(
   }
 }
 
+// the launch behind both entry points: the target of row (b, t) is caps[b*L + t + tgt_off]
+static int eval_rows_launch(const float* logits, const long long* caps, int B, int T, int L, int V, int tgt_off,
+                            const int* lens, float* loss_rows, int* pred, int* rank, void* stream) {
+  const hipStream_t st = as_stream(stream);
+  if (V % 4 == 0 && aligned16(logits))
+    hipLaunchKernelGGL(eval_rows_kernel<true>, dim3(B * T), dim3(EVAL_T), 0, st, logits, caps, T, L, V, tgt_off,
+                       lens, loss_rows, pred, rank);
+  else
+    hipLaunchKernelGGL(eval_rows_kernel<false>, dim3(B * T), dim3(EVAL_T), 0, st, logits, caps, T, L, V, tgt_off,
+                       lens, loss_rows, pred, rank);
+  CAPMI_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int capmi_eval_rows(const float* logits, const long long* caps, int B, int T, int L, int V,
                                const int* lens, float* loss_rows, int* pred, int* rank, void* stream) {
   CAPMI_REQUIRE(logits && caps && loss_rows && pred, CAPMI_EINVAL);
   CAPMI_REQUIRE(B > 0 && T > 0 && V > 0 && L > T && (long long)B * T <= INT_MAX, CAPMI_EINVAL);
-  const hipStream_t st = as_stream(stream);
-  if (V % 4 == 0 && aligned16(logits))
-    hipLaunchKernelGGL(eval_rows_kernel<true>, dim3(B * T), dim3(EVAL_T), 0, st, logits, caps, T, L, V, lens,
-                       loss_rows, pred, rank);
-  else
-    hipLaunchKernelGGL(eval_rows_kernel<false>, dim3(B * T), dim3(EVAL_T), 0, st, logits, caps, T, L, V, lens,
-                       loss_rows, pred, rank);
-  CAPMI_LAUNCH_CHECK();
-  return 0;
+  return eval_rows_launch(logits, caps, B, T, L, V, 1, lens, loss_rows, pred, rank, stream);
+}
+
+extern "C" int capmi_eval_rows_at(const float* logits, const long long* caps, int B, int T, int L, int V,
+                                  int tgt_off, const int* lens, float* loss_rows, int* pred, int* rank,
+                                  void* stream) {
+  CAPMI_REQUIRE(logits && caps && loss_rows && pred, CAPMI_EINVAL);
+  CAPMI_REQUIRE(B > 0 && T > 0 && V > 0 && tgt_off >= 0 && (long long)L >= (long long)T + tgt_off &&
+                    (long long)B * T <= INT_MAX,
+                CAPMI_EINVAL);
+  return eval_rows_launch(logits, caps, B, T, L, V, tgt_off, lens, loss_rows, pred, rank, stream);
 }
 
 // --------------------------------------------------------------------------------------
@@ -205,6 +223,54 @@ extern "C" int capmi_eval_captions(const float* loss_rows, const int* rank, cons
   CAPMI_REQUIRE(B > 0 && T > 0 && P > 0 && (long long)B * T <= INT_MAX, CAPMI_EINVAL);
   hipLaunchKernelGGL(eval_captions_kernel, dim3(B), dim3(EVAL_T), 0, as_stream(stream), loss_rows, rank,
                      alphas, lens, T, P, alpha_c, cap_ce, cap_reg, cap_loss, cap_top1, cap_top5);
+  CAPMI_LAUNCH_CHECK();
+  return 0;
+}
+
+// --------------------------------------------------------------------------------------
+// per caption without the attention regulariser (the baseline model's validation loss is the plain CE mean):
+// eval_captions_kernel's CE and count sums, thread -> element assignment and trees unchanged
+// --------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(EVAL_T) eval_captions_ce_kernel(
+    const float* __restrict__ loss_rows, const int* __restrict__ rank, const int* __restrict__ lens, int T,
+    float* __restrict__ cap_ce, int* __restrict__ cap_top1, int* __restrict__ cap_top5) {
+  __shared__ float red[16];
+  __shared__ int redi[16];
+  const int b = blockIdx.x;
+  const int n = eval_len(lens, b, T);
+  if (n == 0) {
+    if (threadIdx.x == 0) {
+      cap_ce[b] = 0.f;
+      cap_top1[b] = 0;
+      cap_top5[b] = 0;
+    }
+    return;
+  }
+  const long long row0 = (long long)b * T;
+  float ce = 0.f;
+  int c1 = 0, c5 = 0;
+  for (int t = threadIdx.x; t < n; t += EVAL_T) {
+    ce += loss_rows[row0 + t];
+    const int rk = rank[row0 + t];
+    c1 += rk == 0 ? 1 : 0;
+    c5 += (rk >= 0 && rk < 5) ? 1 : 0;
+  }
+  ce = block_sum(ce, red) / (float)n;
+  c1 = block_sum_i(c1, redi);
+  c5 = block_sum_i(c5, redi);
+  if (threadIdx.x == 0) {
+    cap_ce[b] = ce;
+    cap_top1[b] = c1;
+    cap_top5[b] = c5;
+  }
+}
+
+extern "C" int capmi_eval_captions_ce(const float* loss_rows, const int* rank, const int* lens, int B, int T,
+                                      float* cap_ce, int* cap_top1, int* cap_top5, void* stream) {
+  CAPMI_REQUIRE(loss_rows && rank && cap_ce && cap_top1 && cap_top5, CAPMI_EINVAL);
+  CAPMI_REQUIRE(B > 0 && T > 0 && (long long)B * T <= INT_MAX, CAPMI_EINVAL);
+  hipLaunchKernelGGL(eval_captions_ce_kernel, dim3(B), dim3(EVAL_T), 0, as_stream(stream), loss_rows, rank, lens,
+                     T, cap_ce, cap_top1, cap_top5);
   CAPMI_LAUNCH_CHECK();
   return 0;
 }

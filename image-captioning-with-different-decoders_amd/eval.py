@@ -2,11 +2,12 @@
 
     python eval.py basic_att_0.pth.tar --model_type attention [--batch_size 64]
     python eval.py basic_att_0.pth.tar --model_type attention --batch_size 64 --synthetic_size 512
+    python eval.py baseline_0.pth.tar --model_type baseline --batch_size 64 --synthetic_size 512
 
 The reference's arguments are kept: ``checkpoint`` (a file in ./checkpoints), ``--model_type``,
 ``--max_caption_length``, ``--print_freq``. Added: ``--batch_size`` (1, the default, runs the reference's
-one-caption-at-a-time ``evaluate``; larger runs ``models.attention.evaluate_batched``, whose per-caption
-numbers are the same), ``--synthetic_size`` / ``--vocab_size`` / ``--synthetic_len`` (COCO-shaped synthetic
+one-caption-at-a-time ``evaluate``; larger runs ``evaluate_batched`` of models.attention / models.baseline,
+whose per-caption numbers are the same),``--synthetic_size`` / ``--vocab_size`` / ``--synthetic_len`` (COCO-shaped synthetic
 captions of ragged lengths instead of the COCO 'val' set) and ``--trusted_checkpoint`` (as train.py: the
 reference's whole-module checkpoints are pickles). The metrics are printed and written to
 <PathConfig.eval_data>/<checkpoint stem>.json.
@@ -40,7 +41,7 @@ def parse_args(argv=None):
     parser.add_argument('--print_freq', type=int, default=1, help='print training/validation stats every __ batches.')
     # capmi additions
     parser.add_argument('--batch_size', type=int, default=1,
-                        help='captions per step; 1 is the reference loop, > 1 the batched pass (attention model).')
+                        help='captions per step; 1 is the reference loop, > 1 the batched pass.')
     parser.add_argument('--synthetic_size', type=int, default=0,
                         help='evaluate on this many synthetic ragged captions instead of COCO val.')
     parser.add_argument('--vocab_size', type=int, default=8100, help='synthetic vocabulary size.')
@@ -78,6 +79,32 @@ def _attention_models(args, enc_sd, dec_sd, vocab, device):
     return encoder.to(device), decoder.to(device)
 
 
+def _baseline_models(args, enc_sd, dec_sd, device):
+    """Modules for a baseline state_dict checkpoint; every size is read off the tensors."""
+    from models.baseline import BaselineDecoder, BaselineDecoderParams
+    from models.encoder import Encoder
+    if args.synthetic_size > 0:
+        n_vocab = args.vocab_size
+    else:
+        if not os.path.exists(PathConfig.vocab_file):
+            raise SystemError('Must run "python init.py --vocab True" before evaluating.')
+        from vocabulary import load_vocab
+        n_vocab = len(load_vocab())
+    if n_vocab != dec_sd["linear.weight"].shape[0]:
+        raise SystemError(f'checkpoint decodes {dec_sd["linear.weight"].shape[0]} words, the vocabulary has {n_vocab}')
+    encoder = Encoder(enc_sd["embed.weight"].shape[0])
+    encoder.load_state_dict(enc_sd)
+    prm = BaselineDecoderParams()
+    prm.embed_size = dec_sd["embedding.weight"].shape[1]
+    prm.hidden_size = dec_sd["lstm.weight_hh_l0"].shape[1]
+    prm.vocab_size = dec_sd["linear.weight"].shape[0]
+    decoder = BaselineDecoder(prm)
+    if dec_sd["embedding.weight"].dtype == torch.float64:  # GloVe tables stay fp64
+        decoder.load_pretrained_embeddins(dec_sd["embedding.weight"].clone())
+    decoder.load_state_dict(dec_sd)
+    return encoder.to(device), decoder.to(device)
+
+
 def main(argv=None):
     args = parse_args(argv)
     device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
@@ -87,6 +114,10 @@ def main(argv=None):
 
     if args.model_type == 'baseline':
         from models.baseline import evaluate as evaluate_baseline_model
+        if not hasattr(decoder, 'state_dict'):  # state_dict checkpoint (the default format)
+            encoder, decoder = _baseline_models(args, encoder, decoder, device)
+        else:
+            encoder, decoder = encoder.to(device), decoder.to(device)
         metrics = evaluate_baseline_model(device, args, encoder, decoder)
     elif args.model_type == 'attention':
         from models.attention import evaluate as evaluate_attention_model, evaluate_batched

@@ -5,7 +5,7 @@ encoder is the capmi EncoderAttention. Image loading / plotting of the reference
 ``caption_images_beam_search`` is the batched form (capmi.beam.BatchedBeamSearch): B images per call."""
 import torch
 
-from capmi.beam import BatchedBeamSearch, BeamSearch
+from capmi.beam import BaselineBatchedBeamSearch, BatchedBeamSearch, BeamSearch
 from vocabulary import END_TOKEN, START_TOKEN
 
 
@@ -27,3 +27,14 @@ def caption_images_beam_search(device, args, imgs, encoder, decoder, vocab):
     with torch.no_grad():
         encoder_out = encoder(imgs)  # (B, 14, 14, 2048)
     return BatchedBeamSearch(decoder, args.beam_size).search(encoder_out, vocab(START_TOKEN), vocab(END_TOKEN))
+
+
+def baseline_caption_images_beam_search(device, args, imgs, encoder, decoder, vocab):
+    """Captions a batch of images (B, 3, H, W) with the baseline model: one ``Encoder`` forward for the batch,
+    then capmi.beam.BaselineBatchedBeamSearch.
+
+    Returns a list of B tuples (caption token ids, [], finished); failure: ([start, end], [], False)."""
+    with torch.no_grad():
+        img_features = encoder(imgs)  # (B, embed_size)
+    return BaselineBatchedBeamSearch(decoder, args.beam_size).search(img_features, vocab(START_TOKEN),
+                                                                     vocab(END_TOKEN))

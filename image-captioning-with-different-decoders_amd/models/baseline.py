@@ -141,5 +141,152 @@ def train(device, args):
           f'{time.time() - train_start:.4f} seconds.')
 
 
+def _eval_dataset(args):
+    """``args.dataset`` when the caller supplies one (items ``(img, caption)``, a ``vocab``), synthetic ragged
+    captions for ``synthetic_size > 0``, else the reference's COCO 'val' set (needs the dataset)."""
+    dataset = getattr(args, "dataset", None)
+    if dataset is not None:
+        return dataset
+    n = int(getattr(args, "synthetic_size", 0) or 0)
+    if n > 0:
+        from capmi.data import SyntheticCOCO
+        return SyntheticCOCO(n, V=int(getattr(args, "vocab_size", 8100)), L=int(getattr(args, "synthetic_len", 25)),
+                             ragged=True)
+    from dataset import COCODataset  # real COCO path (pycocotools, nltk, images)
+    return COCODataset(mode='val', caption_max_len=getattr(args, "max_caption_length", -1))
+
+
+def _eval_loader(args, dataset, batch_size):
+    from torch.nn.utils.rnn import pad_sequence
+    pad_idx = dataset.vocab(PAD_TOKEN)
+
+    def collate_fn(data):
+        imgs, captions = list(zip(*data))[:2]
+        return (torch.stack(imgs, dim=0), pad_sequence(captions, batch_first=True, padding_value=pad_idx),
+                [len(c) for c in captions])  # true lengths
+
+    return torch.utils.data.DataLoader(dataset=dataset, batch_size=int(batch_size), shuffle=False,
+                                       num_workers=int(getattr(args, "workers", 0) or 0), collate_fn=collate_fn)
+
+
 def evaluate(device, args, encoder, decoder):
-    raise NotImplementedError("evaluation / caption scoring is not part of the training path")
+    """Reference :267-374: one teacher-forced pass over the validation set at batch 1. Step 0 is fed the image
+    feature and scored against START, step t the embedding of caption[t-1] against caption[t]; loss = the plain
+    CE mean over the caption's n rows; hypotheses = the greedy tokens, references = the caption repeated n
+    times, both with START / END / PAD removed.
+
+    ``args.batch_size`` (default 1) above 1 runs ``evaluate_batched``, whose per-caption numbers are the same.
+    The loop goes through ``decoder.forward``: plain nn.LSTM on CPU tensors, capmi.baseline_fn on HIP tensors.
+    Caption scoring (metric.get_eval_score) is attempted and skipped when unavailable: the returned dict then
+    holds the losses, references and hypotheses."""
+    from metric import get_eval_score
+    from vocabulary import END_TOKEN, START_TOKEN
+    batch_size = int(getattr(args, "batch_size", 1) or 1)
+    if batch_size > 1:
+        return evaluate_batched(device, args, encoder, decoder, batch_size=batch_size)
+    dataset = _eval_dataset(args)
+    vocab = dataset.vocab
+    drop = {vocab(START_TOKEN), vocab(END_TOKEN), vocab(PAD_TOKEN)}
+    loader = _eval_loader(args, dataset, 1)
+    print_freq = int(getattr(args, "print_freq", 1) or 1)
+    references, hypotheses, losses = [], [], []
+    accum_loss = AccumulatingMetric()
+    decoder.eval()
+    encoder.eval()
+    num_batches = len(loader)
+    start_time = time.time()
+    with torch.no_grad():
+        for batch_idx, (imgs, captions, _) in enumerate(loader):
+            imgs, captions = imgs.to(device), captions.to(device)
+            scores = decoder(encoder(imgs), captions)  # (1, n, V)
+            loss = nn.functional.cross_entropy(scores.reshape(-1, scores.shape[2]), captions.reshape(-1))
+            n = captions.shape[1]
+            accum_loss.update(loss.item(), n)
+            losses.append(loss.item())
+            for cap in captions.tolist():
+                ref = [w for w in cap if w not in drop]
+                references.append([ref for _ in cap])  # reference :345-350
+            preds = torch.max(scores, dim=2)[1].tolist()
+            hypotheses.extend([[w for w in p if w not in drop] for p in preds])
+            if batch_idx % print_freq == 0:
+                print(f'Batch {batch_idx+1}/{num_batches}, Loss {accum_loss.avg():.4f}')
+    try:
+        metrics = get_eval_score(references, hypotheses)
+    except (NotImplementedError, ImportError):
+        metrics = {"references": references, "hypotheses": hypotheses}
+    metrics['losses'] = losses
+    print(f'Checkpoint {getattr(args, "checkpoint", None)} finished evaluation in '
+          f'{time.time() - start_time:.4f} seconds.')
+    return metrics
+
+
+def evaluate_batched(device, args, encoder, decoder, dataset=None, batch_size=64):
+    """The validation pass of ``evaluate`` over ``batch_size`` captions per step, with per-caption results
+    equal to what the reference computes one caption at a time (reference :267-374 at batch 1).
+
+    Captions are taken in dataset order (no shuffle), padded to the batch maximum and passed with their true
+    lengths. Per batch: one encoder forward, capmi.baseline_eval.BaselineTeacherForcedEval (loss, greedy tokens
+    and top-1 / top-5 counts on the device), one asynchronous copy of the small result buffer to pinned host
+    memory; the device is synchronised only every ``print_freq`` batches and at the end. The vocabulary is the
+    dataset's (the baseline decoder has none).
+
+    Returns a JSON-serialisable dict: the capmi.scoring.caption_scores keys, ``losses`` (per caption, dataset
+    order), ``loss`` (their average weighted by caption length n), ``top1_acc`` / ``top5_acc`` over all scored
+    rows, ``references`` and ``hypotheses`` (as ``evaluate`` builds them)."""
+    from capmi import baseline_eval
+    from capmi.scoring import caption_scores
+    from vocabulary import END_TOKEN, START_TOKEN
+    if dataset is None:
+        dataset = _eval_dataset(args)
+    vocab = dataset.vocab
+    drop = {vocab(START_TOKEN), vocab(END_TOKEN), vocab(PAD_TOKEN)}
+    loader = _eval_loader(args, dataset, batch_size)
+    print_freq = int(getattr(args, "print_freq", 1) or 1)
+    on_gpu = torch.device(device).type == "cuda"
+    tf_eval = baseline_eval.BaselineTeacherForcedEval(decoder)
+    evaluate_batched.last_eval = tf_eval  # (tests: its last_stats)
+    references, hypotheses, losses = [], [], []
+    hits1 = hits5 = rows = 0
+    accum_loss = AccumulatingMetric()
+    decoder.eval()
+    encoder.eval()
+    num_batches = len(loader)
+    start_time = time.time()
+    pending = []
+
+    def drain():
+        nonlocal hits1, hits5, rows
+        if on_gpu:
+            torch.cuda.synchronize()
+        for host, caps_h, lengths, T in pending:
+            res = baseline_eval.unpack(host, len(lengths), T)
+            loss_h, pred_h = res["cap_loss"].tolist(), res["pred"].tolist()
+            hits1 += int(res["top1"].sum())
+            hits5 += int(res["top5"].sum())
+            for i, n in enumerate(lengths):
+                accum_loss.update(loss_h[i], n)
+                losses.append(loss_h[i])
+                rows += n
+                ref = [w for w in caps_h[i][:n] if w not in drop]
+                references.append([ref for _ in range(n)])  # reference :345-350, at this caption's own length
+                hypotheses.append([w for w in pred_h[i][:n] if w not in drop])
+        del pending[:]
+
+    with torch.no_grad():
+        for batch_idx, (imgs, captions, caption_lengths) in enumerate(loader):
+            imgs = imgs.to(device, non_blocking=True)
+            res = tf_eval(encoder(imgs), captions.to(device, non_blocking=True), caption_lengths)
+            packed = res["packed"]
+            host = torch.empty(packed.shape, dtype=packed.dtype, pin_memory=on_gpu)
+            host.copy_(packed, non_blocking=True)
+            pending.append((host, captions.tolist(), caption_lengths, res["pred"].shape[1]))
+            if batch_idx % print_freq == 0:
+                drain()
+                print(f'Batch {batch_idx+1}/{num_batches}, Loss {accum_loss.avg():.4f}')
+        drain()
+    metrics = caption_scores(references, hypotheses)
+    metrics.update(losses=losses, loss=accum_loss.avg(), top1_acc=hits1 / max(rows, 1), top5_acc=hits5 / max(rows, 1),
+                   references=references, hypotheses=hypotheses)
+    print(f'Checkpoint {getattr(args, "checkpoint", None)} finished evaluation in '
+          f'{time.time() - start_time:.4f} seconds.')
+    return metrics

@@ -578,6 +578,35 @@ int capmi_eval_captions(const float* loss_rows, const int* rank, const float* al
                         float* cap_loss, int* cap_top1, int* cap_top5, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Baseline (LSTM) captioner at inference: validation and beam search (reference models/baseline.py:81-111,
+ * 267-374; csrc/baseline_step.hip, csrc/eval.hip). New symbols only, nothing existing changed.
+ * ---------------------------------------------------------------------- */
+/* One timestep of a single-layer LSTM over R rows in one launch (gate order i,f,g,o as torch.nn.LSTM):
+ *   gates[r] = (pre ? pre[r] : 0) + (x ? x[r] W_ih^T : 0) + (h_prev ? h_prev[r] W_hh^T : 0) + b_ih + b_hh
+ *   c = sig(f) c_prev + sig(i) tanh(g);  h = sig(o) tanh(c)
+ * pre [R][4H] (row stride ld_pre >= 4H), x [R][M] (ld_x), h_prev / c_prev [R][H] (ld_h / ld_c), W_ih [4H][M]
+ * and W_hh [4H][H] contiguous, b_ih / b_hh [4H]; every one optional (NULL), but at least one of pre / x /
+ * h_prev is required, W_ih with x and W_hh with h_prev; c_prev NULL = zeros. Writes h_out / c_out [R][H]
+ * (contiguous) only: no gate tensor, no history. fp32-accurate (three-term bf16 split, fp32 accumulation).
+ * A row's result depends on that row's inputs and on (M, H) alone: not on R, not on its place in the batch.
+ * CAPMI_EINVAL unless R, H > 0, M % 4 == 0 (M > 0 with x), H % 4 == 0, ld_x % 4 == 0 and ld_h % 4 == 0, the
+ * bases of x / h_prev / W_ih / W_hh 16-byte aligned, and h_out / c_out distinct from each other and from
+ * h_prev / c_prev. */
+int capmi_lstm_step_fwd(const float* pre, long long ld_pre, const float* x, long long ld_x, int M,
+                        const float* h_prev, long long ld_h, const float* c_prev, long long ld_c,
+                        const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, int R,
+                        int H, float* h_out, float* c_out, void* stream);
+/* capmi_eval_rows with the target column given: tgt = caps[b*L + t + tgt_off], tgt_off >= 0 and
+ * L >= T + tgt_off (capmi_eval_rows is tgt_off = 1; the baseline model scores step t against caps[t]: 0).
+ * lens, clamping, out-of-range targets, pred, rank and inactive rows exactly as capmi_eval_rows. */
+int capmi_eval_rows_at(const float* logits, const long long* caps, int B, int T, int L, int V, int tgt_off,
+                       const int* lens, float* loss_rows, int* pred, int* rank, void* stream);
+/* capmi_eval_captions without alphas / regulariser: n = lens[b] clamped to [0, T] (NULL: T), cap_ce[b] =
+ * sum_{t<n} loss_rows[b*T+t] / n, cap_top1 / cap_top5 as there, n == 0: all three 0. Fixed reduction order. */
+int capmi_eval_captions_ce(const float* loss_rows, const int* rank, const int* lens, int B, int T,
+                           float* cap_ce, int* cap_top1, int* cap_top5, void* stream);
+
+/* ------------------------------------------------------------------------
  * Optimiser (train_utils.py:2-12 clamp + torch.optim.Adam, models/attention.py:352-355,423-430)
  * p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps) with g clamped to +-clip first.
  * step_dev == NULL: bc1 = 1 - beta1^t and bc2_sqrt = sqrt(1 - beta2^t) as passed (host step t);
