@@ -168,6 +168,12 @@ _SIGS = {
     "capmi_resize_taps_max": [c_int, c_int],
     "capmi_split3_bf16": [c_vp, c_ll, c_vp, c_vp],
     "capmi_bn_relu_split3": [c_vp, c_vp, c_vp, c_ll, c_int, c_vp, c_vp],
+    "capmi_bert_embed_ln": [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_float, c_vp,
+                            c_vp],
+    "capmi_add_ln": [c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_float, c_vp, c_vp],
+    "capmi_bias_gelu": [c_vp, c_vp, c_ll, c_int, c_ll, c_vp],
+    "capmi_bert_attention": [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_ll, c_vp],
+    "capmi_segment_sum_rows": [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp],
     "capmi_timing_event_create": [ctypes.POINTER(c_vp)],
     "capmi_timing_event_destroy": [c_vp],
     "capmi_timing_event_record": [c_vp, c_vp],

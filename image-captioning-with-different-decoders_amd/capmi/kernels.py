@@ -864,6 +864,80 @@ def embed_scatter_add(dx, ld_dx, caps, B, L, T, bt_dev, M, demb):
          int(demb.dtype == torch.float64), stream())
 
 
+# --------------------------------------------------------------------------------------
+# BERT encoder forward (capmi/bert.py): ragged packed rows, one word piece per row
+# --------------------------------------------------------------------------------------
+I32 = torch.int32
+
+
+def _rows_ok(name, t, rows, cols):
+    if not t.is_contiguous() or t.numel() < rows * cols:
+        raise ValueError(f"{name}: needs a contiguous buffer of at least {rows} x {cols} elements")
+
+
+def bert_embed_ln(word_emb, pos_emb, type_emb, ids, pos, rows, gamma, beta, eps, out):
+    """out[r] = LayerNorm(word_emb[ids[r]] + pos_emb[pos[r]] + type_emb[0]); ids / pos int32 [rows]."""
+    _cuda(word_emb, pos_emb, type_emb, gamma, beta, out)
+    _cuda(ids, pos, dtype=I32)
+    H = word_emb.shape[1]
+    if pos_emb.shape[1] != H or type_emb.shape[-1] != H or gamma.numel() != H or beta.numel() != H:
+        raise ValueError("bert_embed_ln: hidden sizes differ")
+    if ids.numel() < rows or pos.numel() < rows:
+        raise ValueError("bert_embed_ln: index arrays shorter than rows")
+    for t in (word_emb, pos_emb, type_emb):
+        assert t.is_contiguous()
+    _rows_ok("bert_embed_ln out", out, rows, H)
+    call("capmi_bert_embed_ln", ptr(word_emb), ptr(pos_emb), ptr(type_emb), ptr(ids), ptr(pos), rows, H,
+         word_emb.shape[0], pos_emb.shape[0], ptr(gamma), ptr(beta), float(eps), ptr(out), stream())
+
+
+def add_ln(x, bias, residual, rows, hidden, gamma, beta, eps, out):
+    """out = LayerNorm(x + bias + residual) over [rows][hidden] (bias None: not added)."""
+    _cuda(x, bias, residual, gamma, beta, out)
+    for n, t in (("x", x), ("residual", residual), ("out", out)):
+        _rows_ok(f"add_ln {n}", t, rows, hidden)
+    if gamma.numel() != hidden or beta.numel() != hidden or (bias is not None and bias.numel() != hidden):
+        raise ValueError("add_ln: gamma / beta / bias must have hidden elements")
+    if out.data_ptr() in (x.data_ptr(), residual.data_ptr()):
+        raise ValueError("add_ln: out must not alias an input")
+    call("capmi_add_ln", ptr(x), ptr(bias), ptr(residual), rows, hidden, ptr(gamma), ptr(beta), float(eps),
+         ptr(out), stream())
+
+
+def bias_gelu(x, bias, rows, cols, ld=None):
+    """In place x[r][c] = gelu_erf(x[r][c] + bias[c]) (bias None: not added)."""
+    _cuda(x, bias)
+    ld = cols if ld is None else ld
+    if not x.is_contiguous() or x.numel() < (rows - 1) * ld + cols or (bias is not None and bias.numel() != cols):
+        raise ValueError("bias_gelu: buffer sizes")
+    call("capmi_bias_gelu", ptr(x), ptr(bias), rows, cols, ld, stream())
+
+
+def bert_attention(qkv, seq_off, nseq, rows, max_len, heads, head_dim, out, ld_out=None):
+    """out[rows][heads*head_dim] = per-(sequence, head) softmax(q k^T / sqrt(d)) v from the fused
+    qkv[rows][3*heads*head_dim]; seq_off int32 [nseq + 1] row offsets; max_len >= the longest sequence."""
+    _cuda(qkv, out)
+    _cuda(seq_off, dtype=I32)
+    H = heads * head_dim
+    ld_out = H if ld_out is None else ld_out
+    _rows_ok("bert_attention qkv", qkv, rows, 3 * H)
+    if not out.is_contiguous() or out.numel() < (rows - 1) * ld_out + H or seq_off.numel() < nseq + 1:
+        raise ValueError("bert_attention: buffer sizes")
+    call("capmi_bert_attention", ptr(qkv), ptr(seq_off), nseq, rows, max_len, heads, head_dim, ptr(out), ld_out,
+         stream())
+
+
+def segment_sum_rows(x, seg, nseg, rows, hidden, out):
+    """out[s] = sum of x[seg[s]:seg[s+1]] (dense [nseg][hidden]); seg int32 [nseg + 1]."""
+    _cuda(x, out)
+    _cuda(seg, dtype=I32)
+    _rows_ok("segment_sum_rows x", x, rows, hidden)
+    _rows_ok("segment_sum_rows out", out, nseg, hidden)
+    if seg.numel() < nseg + 1:
+        raise ValueError("segment_sum_rows: seg needs nseg + 1 entries")
+    call("capmi_segment_sum_rows", ptr(x), ptr(seg), nseg, rows, hidden, ptr(out), stream())
+
+
 TILE_128, TILE_64, TILE_128x64, TILE_AUTO = CAPMI_TILE_128, CAPMI_TILE_64, CAPMI_TILE_128x64, CAPMI_TILE_AUTO
 BNB_RELU_Y, BNB_RELU_OUT = 0, 1
 

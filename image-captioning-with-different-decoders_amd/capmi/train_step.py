@@ -35,6 +35,7 @@ stage (FineTuneRunner.backward's ``on_layer``); clamp + Adam once all are in
 those points and the collectives are issued between the segments' replays. ``schedule`` lists
 what the last call issued, in order ("seg0", "ar:dec", "seg1", "ar:layer4", ...).
 """
+import contextlib
 import os
 
 import torch
@@ -118,6 +119,44 @@ class AttentionTrainStep:
 
     def _grads(self):
         return {n: self.params[n].grad for n in self.need}
+
+    # ------------------------------------- word features computed outside the graphs (capmi.bert.BertEmbedder)
+    def _ext_embedder(self):
+        """The decoder's ``bert_embedder`` when it cannot be captured (``graph_safe = False``: the real BERT
+        forward sizes its ragged batch on the host from the token values), else None. Such features are
+        computed eagerly into a static buffer before each replay; the captured step reads that buffer."""
+        if not getattr(self.decoder, "use_bert", False):
+            return None
+        emb = getattr(self.decoder, "bert_embedder", None)
+        return emb if emb is not None and getattr(emb, "graph_safe", True) is False else None
+
+    def _static_feats(self, st):
+        emb = self._ext_embedder()
+        if emb is not None:
+            st["bert"] = emb(st["caps"])
+
+    @contextlib.contextmanager
+    def _feats_from(self, st):
+        """While warming up / capturing: the decoder takes its word features from st["bert"]."""
+        emb = self._ext_embedder()
+        if emb is None:
+            yield
+            return
+        self.decoder.bert_embedder = lambda caps: st["bert"]
+        try:
+            yield
+        finally:
+            self.decoder.bert_embedder = emb
+
+    def _refresh_feats(self, st, host_tokens):
+        """Before a replay: the features of the batch now in st["caps"], into the buffer the graph reads."""
+        emb = self._ext_embedder()
+        if emb is not None:
+            emb(st["caps"], out=st["bert"], host_tokens=host_tokens)
+
+    def _host_tokens(self, captions):
+        """The caption tokens on the host, when an out-of-graph embedder needs them (one small copy)."""
+        return captions.detach().cpu() if self._ext_embedder() is not None else None
 
     @staticmethod
     def _stage_buckets(encoder, opt):
@@ -341,10 +380,12 @@ class AttentionTrainStep:
         for slot in range(2):
             pg.append({"imgs": imgs.detach().clone(), "caps": captions.detach().clone(),
                        "lens": list(caption_lengths), "slot": slot})
+        for st in pg:
+            self._static_feats(st)
         torch.cuda.synchronize()
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
+        with torch.cuda.stream(s), self._feats_from(pg[0]):
             for _ in range(warmup):
                 self._encode_into(pg[0]["imgs"], feats[0], dup)
                 self._dec_body(feats[0], pg[0]["caps"], pg[0]["lens"], with_update=False, dup=dup)
@@ -361,18 +402,19 @@ class AttentionTrainStep:
             st["feats"] = feats[slot]  # the graphs hold raw pointers: keep the buffer alive
             if self.capture_hook is not None:
                 self.capture_hook(f"dec{slot}")
-            if upd:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    st["loss"] = self._dec_body(feats[slot], st["caps"], st["lens"], with_update=True,
-                                                dup=dup)
-                st["g_dec"] = g
-            else:
-                # data parallel: two graphs cut where the fc gradients are final, so their all-reduce
-                # is issued between the replays and runs beside the backward-through-time graph
-                st["loss"], st["g_dec"], st["g_dec2"] = self._capture_split(
-                    lambda cut: self._dec_body(feats[slot], st["caps"], st["lens"], with_update=False, on_fc=cut,
-                                               dup=dup))
+            with self._feats_from(st):
+                if upd:
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        st["loss"] = self._dec_body(feats[slot], st["caps"], st["lens"], with_update=True,
+                                                    dup=dup)
+                    st["g_dec"] = g
+                else:
+                    # data parallel: two graphs cut where the fc gradients are final, so their all-reduce
+                    # is issued between the replays and runs beside the backward-through-time graph
+                    st["loss"], st["g_dec"], st["g_dec2"] = self._capture_split(
+                        lambda cut: self._dec_body(feats[slot], st["caps"], st["lens"], with_update=False, on_fc=cut,
+                                                   dup=dup))
         torch.cuda.synchronize()
         pg[0]["pins"] = self._pins()
         self.counts["capture"] += 1
@@ -453,6 +495,7 @@ class AttentionTrainStep:
         slot = self._slot
         self._slot ^= 1
         st = pg[slot]
+        st["host_caps"] = self._host_tokens(captions)
         # the slot's static inputs and features were last read by the decoder of the previous call
         self.s_enc.wait_stream(cur)
         if self._ev_dec is not None:
@@ -486,6 +529,7 @@ class AttentionTrainStep:
             self.s_dec.wait_event(ev)
             self.s_dec.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(self.s_dec):
+                self._refresh_feats(st, st.get("host_caps"))
                 st["g_dec"].replay()
                 self.replayed.append(f"dec{st['slot']}")
                 if self.ctx.distributed:
@@ -569,6 +613,7 @@ class AttentionTrainStep:
             st["imgs"].copy_(imgs, non_blocking=True)
         if captions.data_ptr() != st["caps"].data_ptr():
             st["caps"].copy_(captions, non_blocking=True)
+        self._refresh_feats(st, self._host_tokens(captions))
         self.schedule = []
         if self._segs is None:
             self._graph.replay()
@@ -604,16 +649,18 @@ class AttentionTrainStep:
         # call still applies exactly one update; the BN running statistics and the dropout seed
         # counter the warm-up forwards advance are restored afterwards (graph == eager).
         snap = self._snapshot()
+        self._static_feats(st)
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         self._capturing = True
         try:
-            with torch.cuda.stream(s):
-                for _ in range(warmup):
-                    self._body(st["imgs"], st["caps"], st["lens"], with_update=False)
-            torch.cuda.current_stream().wait_stream(s)
-            self._restore(snap)
-            self._capture_graphs(st, upd)
+            with self._feats_from(st):
+                with torch.cuda.stream(s):
+                    for _ in range(warmup):
+                        self._body(st["imgs"], st["caps"], st["lens"], with_update=False)
+                torch.cuda.current_stream().wait_stream(s)
+                self._restore(snap)
+                self._capture_graphs(st, upd)
         finally:
             self._capturing = False
 

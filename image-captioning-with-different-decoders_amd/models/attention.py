@@ -67,7 +67,9 @@ class AttentionDecoder(nn.Module):
         # reference :96-100 loads bert-base-uncased by name (a network fetch, unavailable offline).
         # The BERT variant is kept as its interface: ``bert_embedder(encoded_captions)`` returns
         # the (B, L+1, 768) word-level layer-11 features that _create_bert_embeddings (:166-215)
-        # builds; plug in a local BERT, or capmi.data.SyntheticBertEmbedder for benchmarks.
+        # builds: capmi.bert.BertEmbedder over a local checkpoint (train.py --bert_path; the real BERT
+        # forward on the HIP kernels), or capmi.data.SyntheticBertEmbedder for benchmarks. A plain
+        # attribute, not a submodule: state-dict keys and checkpoints are the same with and without it.
         self.bert_embedder = None
         self.compute_precision = "fp32"  # set_compute_precision
 
@@ -178,6 +180,17 @@ def _build_models(args, vocab, device):
             decoder.load_pretrained_embeddins(dec_sd["embedding.weight"].clone())
         decoder.load_state_dict(dec_sd)
         decoder.fine_tune_embeddings(args.fine_tune_embedding)
+
+    if args.use_bert:
+        # the real BERT features (reference :96-100) from a LOCAL checkpoint: --bert_path, else
+        # PathConfig.bert_dir when that directory exists; with neither, the first step raises as before
+        from pathconf import PathConfig
+        bert_path = getattr(args, 'bert_path', None)
+        if bert_path is None and os.path.isdir(PathConfig.bert_dir):
+            bert_path = PathConfig.bert_dir
+        if bert_path is not None:
+            from capmi.bert import build_embedder
+            decoder.bert_embedder = build_embedder(decoder, bert_path, device)
 
     return encoder, decoder, start_epoch, metrics, opt_state, enc_opt_state
 

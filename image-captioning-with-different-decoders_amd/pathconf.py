@@ -9,3 +9,4 @@ class PathConfig:
     train_img_dir = 'cocoapi/images/train2014'
     val_img_dir = 'cocoapi/images/val2014'
     eval_data = 'eval_data'
+    bert_dir = 'pkldata/bert-base-uncased'  # local BERT checkpoint for --use_bert (used when it exists)

@@ -51,6 +51,9 @@ def parse_args(argv=None):
     parser.add_argument('--synthetic', type=bool, default=False, help='COCO-shaped synthetic data.')
     parser.add_argument('--synthetic_size', type=int, default=0, help='samples in the synthetic dataset.')
     parser.add_argument('--vocab_size', type=int, default=8100, help='synthetic vocabulary size.')
+    parser.add_argument('--bert_path', type=str, default=None,
+                        help='local BERT checkpoint directory (pytorch_model.bin or model.safetensors, config.json, '
+                             'vocab.txt) for --use_bert; never fetched by name.')
     return parser.parse_args(argv)
 
 

@@ -631,6 +631,36 @@ int capmi_split3_bf16(const float* in, long long n, void* out, void* stream);
 int capmi_bn_relu_split3(const float* y, const float* scale, const float* shift, long long rows, int C, void* out,
                          void* stream);
 
+/* ---- frozen BERT encoder forward (capmi/bert.py; reference models/attention.py:166-215) ----
+ * The non-GEMM kernels of a BERT layer stack over RAGGED packed sequences: row r of every activation is
+ * one word piece, sequence s owns rows [seq_off[s], seq_off[s+1]). fp32 in, fp32 statistics, fp32 out.
+ * All pointers 16-B aligned, hidden % 4 == 0, hidden <= 8192 (the LayerNorm row is held in LDS). Index
+ * arrays are int32 device data; out-of-range entries are clamped in the kernel, never followed.
+ * Added without an ABI bump (purely additive). */
+/* out[r] = LayerNorm(word_emb[ids[r]] + pos_emb[pos[r]] + type_emb[0]) * gamma + beta */
+int capmi_bert_embed_ln(const float* word_emb, const float* pos_emb, const float* type_emb, const int* ids,
+                        const int* pos, int rows, int hidden, int vocab, int npos, const float* gamma,
+                        const float* beta, float eps, float* out, void* stream);
+/* out[r] = LayerNorm(x[r] + bias + residual[r]) * gamma + beta; bias may be NULL (already added by the
+ * GEMM epilogue); out must not alias x or residual */
+int capmi_add_ln(const float* x, const float* bias, const float* residual, int rows, int hidden,
+                 const float* gamma, const float* beta, float eps, float* out, void* stream);
+/* in place x[r][c] = gelu(x[r][c] + bias[c]), gelu(v) = v/2 (1 + erf(v / sqrt 2)); bias may be NULL;
+ * cols % 4 == 0, ld % 4 == 0 */
+int capmi_bias_gelu(float* x, const float* bias, long long rows, int cols, long long ld, void* stream);
+/* Multi-head self-attention over ragged sequences, reading the fused projection qkv[total_rows][3 * hidden]
+ * (q | k | v, hidden = heads * head_dim) in place: for every sequence s and head h,
+ * out[r][h*64 .. h*64+63] = softmax_j(q_r . k_j / sqrt(head_dim)) v_j over the rows j of s (full attention, no
+ * mask). head_dim must be 64 and max_len (>= the longest sequence; sizes the grid) 1..512, else CAPMI_ERANGE.
+ * One wave per (64 queries, head, sequence), a query per lane, keys / values in 64-row LDS blocks, max-
+ * subtracted online softmax in fp32. ld_out = row stride of out (>= hidden). */
+int capmi_bert_attention(const float* qkv, const int* seq_off, int nseq, int total_rows, int max_len, int heads,
+                         int head_dim, float* out, long long ld_out, void* stream);
+/* out[s][0:hidden] = sum of x[r][0:hidden] over r in [seg[s], seg[s+1]) (an empty segment: zeros), s < nseg;
+ * out is dense [nseg][hidden]: the (B, L+1, hidden) word-feature tensor */
+int capmi_segment_sum_rows(const float* x, const int* seg, int nseg, int total_rows, int hidden, float* out,
+                           void* stream);
+
 /* ---- kernel timing inside HIP graphs (bench.py's roofline) -------------------------------
  * Timing events whose record becomes a graph node when `stream` is being captured
  * (hipEventRecordExternal), a plain record otherwise; after a replay has completed,
