@@ -88,6 +88,8 @@ _SIGS = {
     "capmi_gemm_sk_ex": [ctypes.POINTER(GemmProblem), c_int, c_int, c_int, c_int, c_vp, c_ll, c_vp],
     "capmi_gemm_sk_plan": [ctypes.POINTER(GemmProblem), c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
     "capmi_last_launch_name": [ctypes.c_char_p, c_int],
+    "capmi_gemm_x3s_stats": [ctypes.POINTER(GemmProblem), c_int, c_vp],
+    "capmi_gemm_x3s_tail": [ctypes.POINTER(GemmProblem), c_int, c_vp, c_vp, c_vp, c_ll, c_vp, c_vp, c_int, c_vp],
     "capmi_splitk_reduce": [c_vp, c_int, c_ll, c_int, c_int, c_ll, c_vp, c_vp, c_ll, c_vp],
     "capmi_colsum": [c_vp, c_int, c_int, c_ll, c_float, c_vp, c_vp, c_int, c_vp],
     "capmi_conv_weight_pack": [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp],

@@ -259,6 +259,30 @@ def gemm_x3s_kernel_name(prob, amode):
     return f"gemm_x3s_kernel<{ncb}, {'true' if prob.in_scale else 'false'}>"
 
 
+def gemm_x3s_stats(prob, amode):
+    """The statistics pass of a CAPMI_GEMM_X3S problem with N = 256: prob.stats as gemm_x3s writes them, bit for
+    bit; C is not touched (capmi_gemm_x3s_stats)."""
+    call("capmi_gemm_x3s_stats", ctypes.byref(prob), amode, stream())
+
+
+def gemm_x3s_tail(prob, amode, scale, shift, other, ld_other, res_scale=None, res_shift=None):
+    """The tail pass (capmi_gemm_x3s_tail): prob.C = relu(acc * scale + shift + other), or with res_scale /
+    res_shift (the product is the residual branch, ``other`` the stored main branch) relu(other * scale + shift +
+    acc * res_scale + res_shift) -- bn_add_relu's operations on the product of prob instead of a stored y."""
+    _cuda(scale, shift, other, res_scale, res_shift)
+    call("capmi_gemm_x3s_tail", ctypes.byref(prob), amode, ptr(scale), ptr(shift), ptr(other), int(ld_other),
+         ptr(res_scale), ptr(res_shift), int(res_scale is not None), stream())
+
+
+def gemm_x3s_stats_kernel_name(prob, amode):
+    return f"gemm_x3s_stats_kernel<4, {'true' if prob.in_scale else 'false'}>"
+
+
+def gemm_x3s_tail_kernel_name(prob, amode, acc_is_residual):
+    b = lambda x: "true" if x else "false"  # noqa: E731
+    return f"gemm_x3s_tail_kernel<4, {b(bool(prob.in_scale))}, {b(acc_is_residual)}>"
+
+
 def gemm_x3d_kernel_name(prob, amode):
     v = [ctypes.c_int(0) for _ in range(5)]
     call("capmi_gemm_sk_plan", ctypes.byref(prob), amode, CAPMI_B_NMAJOR_W, CAPMI_TILE_AUTO, CAPMI_GEMM_X3D,

@@ -147,6 +147,10 @@ _X3_SMALLK = int(os.environ.get("CAPMI_X3_SMALLK", "0"))
 _X3D = os.environ.get("CAPMI_X3D", "1") != "0"
 # x3 mode: layer1's K = 64 1x1 convs on the short-k streaming kernel (CAPMI_X3S=0: off, A/B)
 _X3S = os.environ.get("CAPMI_X3S", "1") != "0"
+# x3 mode: layer1's conv3 (identity blocks) / downsample (layer1.0) computed twice on that kernel -- a statistics
+# pass, then a pass whose epilogue is the bottleneck tail -- instead of stored, re-read and followed by bn_add_relu
+# (CAPMI_X3S_TAIL=0: off, A/B)
+_X3S_TAIL = os.environ.get("CAPMI_X3S_TAIL", "1") != "0"
 # x3 mode (round 4): layer1's 3x3 on the direct conv (gemm_x3c.hip: each input element split once per 32-channel
 # slice instead of once per tap; CAPMI_X3C=0: gemm_x3, A/B)
 _X3C = os.environ.get("CAPMI_X3C", "1") != "0"
@@ -166,6 +170,9 @@ class EncoderRunner:
         # fp32 convs as fp32-accurate three-term bf16 split GEMMs (CAPMI_GEMM_X3, gemm_x3.hip) instead
         # of v_mfma_f32_32x32x2_f32; same fp32 activations, statistics and outputs
         self.x3 = False
+        # x3 mode: layer1's bottleneck tails fused into a recomputed K = 64 conv pass (_conv_tail; mirrors
+        # CAPMI_X3S_TAIL so a test can flip it in-process)
+        self.x3s_tail = _X3S_TAIL
 
     def _workspace(self, N, H, W, device):
         key = (N, H, W, str(device))
@@ -363,6 +370,51 @@ class EncoderRunner:
         del stats
         return Ho, Wo, rows
 
+    def _conv_tail(self, tag, x, conv, bn, other, out, N, H, W, train, in_ss=None, main_ss=None):
+        """conv + BN + residual + ReLU -> the block output, without the raw conv output ever being stored (DESIGN
+        4.25): a K = 64, N = 256 1x1 conv that x3s accepts is computed twice (gemm_x3s.hip) -- a statistics pass,
+        ``bn``'s finalize, then a tail pass whose epilogue applies the BN, adds the other branch, applies the ReLU
+        and stores ``out``. main_ss None: the conv is the main branch (conv3, ``bn`` = bn3) and ``other`` the
+        identity input; else the conv is the downsample (``bn`` its BN), ``other`` the stored conv3 output and
+        main_ss bn3's (scale, shift). train False: running statistics, the tail pass alone. Returns False, with
+        nothing launched, where the route does not apply (switched off, another shape, a batch past the 32-bit
+        offsets, the planner's refusal): the caller then takes the conv -> bn_add_relu path."""
+        co, ci, kh, kw = conv.weight.shape
+        rows = N * H * W
+        if not (self.x3s_tail and _X3S and self.x3 and ci == 64 and co == 256 and kh == 1 and kw == 1
+                and conv.stride[0] == 1 and conv.padding[0] == 0 and rows * co * 4 < (1 << 31)):
+            return False
+        w3 = self._packed_x3(conv)
+        stats = self._ws["stats"] if train else None
+        if in_ss is None:
+            prob, mode = K.problem(rows, co, ci, x, ci, w3, ci, out, co, stats=stats), CAPMI_A_KMAJOR
+        else:
+            geo = dict(N=N, H=H, W=W, Cin=ci, KH=1, KW=1, stride=1, pad=0, Ho=H, Wo=W)
+            prob = K.problem(rows, co, ci, x, 0, w3, ci, out, co, conv=geo, in_scale=in_ss[0], in_shift=in_ss[1],
+                             stats=stats)
+            mode = CAPMI_A_CONV_NHWC
+        if not K.gemm_x3s_ok(prob, mode):
+            return False
+
+        def run(tag, flops, launch, key):
+            if self.conv_hook is not None:
+                self.conv_hook(tag, flops, launch, key)
+            else:
+                launch()
+
+        if train:
+            run(tag, 2.0 * rows * co * ci, lambda: K.gemm_x3s_stats(prob, mode),
+                K.gemm_x3s_stats_kernel_name(prob, mode))
+        s, b = self._bn(self._ws, bn, rows, train)
+        res = main_ss is not None
+        if res:
+            tail = lambda: K.gemm_x3s_tail(prob, mode, main_ss[0], main_ss[1], other, co, s, b)  # noqa: E731
+        else:
+            tail = lambda: K.gemm_x3s_tail(prob, mode, s, b, other, co)  # noqa: E731
+        # priced at 0 flops: its time counts, the conv's algorithmic work is not doubled
+        run(tag + ".tail", 0.0, tail, K.gemm_x3s_tail_kernel_name(prob, mode, res))
+        return True
+
     def _packed_x3(self, conv, tap_inner=False):
         """[3][Cout][K] bf16 split of the packed fp32 weight (B operand of gemm_x3; with ``tap_inner``
         in gemm_x3p's conv k order), refreshed when the weight tensor changes. The fused Adam writes the
@@ -512,15 +564,21 @@ class EncoderRunner:
                 ss1 = self._bn(ws, blk.bn1, r1, train)
                 H2, W2, r2 = self._conv(tag + ".conv2", ws["y1"], blk.conv2, ws["y2"], N, H, W, train, in_ss=ss1)
                 ss2 = self._bn(ws, blk.bn2, r2, train)
-                _, _, r3 = self._conv(tag + ".conv3", ws["y2"], blk.conv3, ws["y3"], N, H2, W2, train, in_ss=ss2)
                 Cout = blk.conv3.out_channels
                 if blk.downsample is not None:
+                    _, _, r3 = self._conv(tag + ".conv3", ws["y2"], blk.conv3, ws["y3"], N, H2, W2, train, in_ss=ss2)
                     s3, b3 = self._bn(ws, blk.bn3, r3, train)  # (the downsample conv reuses the stats buffer)
-                    self._conv(tag + ".downsample", x, blk.downsample[0], ws["yd"], N, H, W, train)
-                    sd, bd = self._bn(ws, blk.downsample[1], r3, train)
-                    K.bn_add_relu(ws["y3"], s3, b3, ws["yd"], xo, r3, Cout, res_scale=sd, res_shift=bd)
+                    # layer1.0: the downsample is the recomputed conv, the stored y3 its tail's other branch
+                    if not self._conv_tail(tag + ".downsample", x, blk.downsample[0], blk.downsample[1], ws["y3"],
+                                           xo, N, H, W, train, main_ss=(s3, b3)):
+                        self._conv(tag + ".downsample", x, blk.downsample[0], ws["yd"], N, H, W, train)
+                        sd, bd = self._bn(ws, blk.downsample[1], r3, train)
+                        K.bn_add_relu(ws["y3"], s3, b3, ws["yd"], xo, r3, Cout, res_scale=sd, res_shift=bd)
                     bns.append(blk.downsample[1])
-                else:
+                # layer1's identity blocks: conv3 recomputed, the block input its tail's other branch
+                elif not self._conv_tail(tag + ".conv3", ws["y2"], blk.conv3, blk.bn3, x, xo, N, H2, W2, train,
+                                         in_ss=ss2):
+                    _, _, r3 = self._conv(tag + ".conv3", ws["y2"], blk.conv3, ws["y3"], N, H2, W2, train, in_ss=ss2)
                     s3, b3 = self._bn(ws, blk.bn3, r3, train)
                     K.bn_add_relu(ws["y3"], s3, b3, x, xo, r3, Cout)
                 bns += [blk.bn1, blk.bn2, blk.bn3]
@@ -712,15 +770,24 @@ class FineTuneRunner:
                 s1, b1, m1 = bnf(blk.bn1, r1)
                 r._conv(tag + ".conv2", y1, blk.conv2, y2, N, H, W, True, in_ss=(s1, b1))
                 s2, b2, m2 = bnf(blk.bn2, r3)
-                r._conv(tag + ".conv3", y2, blk.conv3, y3, N, H2, W2, True, in_ss=(s2, b2))
-                s3, b3, m3 = bnf(blk.bn3, r3)
                 md = sd = bd = None
+                # frozen layer1 (EncoderRunner._conv_tail): an identity block's conv3, or layer1.0's downsample
+                # beside its stored y3, recomputed straight into the block output
+                fused = not trainable and blk.downsample is None and r._conv_tail(
+                    tag + ".conv3", y2, blk.conv3, blk.bn3, x, o, N, H2, W2, True, in_ss=(s2, b2))
+                if not fused:
+                    r._conv(tag + ".conv3", y2, blk.conv3, y3, N, H2, W2, True, in_ss=(s2, b2))
+                    s3, b3, m3 = bnf(blk.bn3, r3)
+                    fused = not trainable and blk.downsample is not None and r._conv_tail(
+                        tag + ".downsample", x, blk.downsample[0], blk.downsample[1], y3, o, N, H, W, True,
+                        main_ss=(s3, b3))
                 if blk.downsample is not None:
-                    r._conv(tag + ".downsample", x, blk.downsample[0], yd, N, H, W, True)
-                    sd, bd, md = bnf(blk.downsample[1], r3)
-                    K.bn_add_relu(y3, s3, b3, yd, o, r3, Cout, res_scale=sd, res_shift=bd)
+                    if not fused:
+                        r._conv(tag + ".downsample", x, blk.downsample[0], yd, N, H, W, True)
+                        sd, bd, md = bnf(blk.downsample[1], r3)
+                        K.bn_add_relu(y3, s3, b3, yd, o, r3, Cout, res_scale=sd, res_shift=bd)
                     bns.append(blk.downsample[1])
-                else:
+                elif not fused:
                     K.bn_add_relu(y3, s3, b3, x, o, r3, Cout)
                 bns += [blk.bn1, blk.bn2, blk.bn3]
                 if trainable:

@@ -1260,6 +1260,22 @@ int gemm_x3s(const capmi_gemm_problem* prob, int amode, int bmode, hipStream_t s
   return gemm_x3s_launch(*prob, lda, tiles, grid, s);
 }
 
+// the two passes that replace "x3s conv -> stored y -> bn_add_relu" (gemm_x3s.hip): x3s_plan's rules, N = 256
+int x3s_pass_plan(const capmi_gemm_problem* prob, int amode, bool need_c, capmi_gemm_problem& p, long long& lda,
+                  int& tiles, int& grid) {
+  CAPMI_REQUIRE(prob != nullptr, CAPMI_EINVAL);
+  p = *prob;
+  if (!need_c && p.C == nullptr) {  // the statistics pass has no C: plan it as the product it stands for
+    p.C = const_cast<float*>(p.A);
+    p.ldc = p.N;
+  }
+  const int rc = x3s_plan(&p, amode, CAPMI_B_NMAJOR_W, lda, tiles, grid);
+  if (rc) return rc;
+  CAPMI_REQUIRE(p.N == 256, CAPMI_EINVAL);
+  if (!need_c) p.C = nullptr;
+  return 0;
+}
+
 int gemm_x3(const capmi_gemm_problem* prob, int amode, int bmode, int tile, void* workspace, long long ws_bytes,
             hipStream_t s) {
   GemmArgs a;
@@ -1284,6 +1300,38 @@ int gemm_x3(const capmi_gemm_problem* prob, int amode, int bmode, int tile, void
   return gemm_x3_launch(a, amode, bn, a.sk_workers, s);
 }
 }  // namespace
+
+extern "C" int capmi_gemm_x3s_stats(const capmi_gemm_problem* prob, int amode, void* stream) {
+  capmi_gemm_problem p;
+  long long lda = 0;
+  int tiles = 0, grid = 0;
+  const int rc = x3s_pass_plan(prob, amode, false, p, lda, tiles, grid);
+  if (rc) return rc;
+  CAPMI_REQUIRE(p.stats != nullptr, CAPMI_EINVAL);
+  if (p.M == 0) return 0;
+  return gemm_x3s_stats_launch(p, lda, tiles, grid, as_stream(stream));
+}
+
+extern "C" int capmi_gemm_x3s_tail(const capmi_gemm_problem* prob, int amode, const float* scale, const float* shift,
+                                   const float* other, long long ld_other, const float* res_scale,
+                                   const float* res_shift, int acc_is_residual, void* stream) {
+  capmi_gemm_problem p;
+  long long lda = 0;
+  int tiles = 0, grid = 0;
+  CAPMI_REQUIRE(scale && shift && other && (acc_is_residual == 0 || acc_is_residual == 1), CAPMI_EINVAL);
+  // the accumulator's own BN: scale / shift as the main branch, res_scale / res_shift as the residual branch
+  CAPMI_REQUIRE(acc_is_residual ? (res_scale && res_shift) : (!res_scale && !res_shift), CAPMI_EINVAL);
+  const int rc = x3s_pass_plan(prob, amode, true, p, lda, tiles, grid);
+  if (rc) return rc;
+  CAPMI_REQUIRE(aligned16(other), CAPMI_EALIGN);
+  CAPMI_REQUIRE(ld_other >= p.N && (long long)p.M * ld_other * 4 < (1LL << 31), CAPMI_EINVAL);
+  // rows past M are dropped by the two descriptors' bounds: a ragged last tile's offsets must not wrap 32 bits
+  CAPMI_REQUIRE(((long long)p.M + 63) * std::max(ld_other, p.ldc) * 4 < (1LL << 32), CAPMI_ERANGE);
+  if (p.M == 0) return 0;
+  p.stats = nullptr;
+  const X3sTail e{scale, shift, other, ld_other, res_scale, res_shift};
+  return gemm_x3s_tail_launch(p, lda, tiles, grid, e, acc_is_residual != 0, as_stream(stream));
+}
 
 extern "C" int capmi_gemm_sk_ex(const capmi_gemm_problem* prob, int amode, int bmode, int tile, int flags,
                                 void* workspace, long long ws_bytes, void* stream) {

@@ -133,6 +133,19 @@ int gemm_x3d_launch(const GemmArgs& a, int amode, int blocks, hipStream_t s);
 // short-k streaming x3 GEMM (gemm_x3s.hip): K = 64, N in {64, 128, 256}, dense rows of lda floats
 // (optional BN prologue), store-only epilogue; persistent grid over 64-row tiles
 int gemm_x3s_launch(const capmi_gemm_problem& p, long long lda, int tiles, int grid, hipStream_t s);
+// the same tile loop without C (statistics only) and with the bottleneck tail as its epilogue (N = 256 only):
+// out = relu(bn(acc) + other) (acc the main branch) or relu(bn(other) + res_bn(acc)) (acc the residual branch)
+struct X3sTail {
+  const float* scale;      // [N] BN of the main branch
+  const float* shift;
+  const float* other;      // [M][ld_other]: the identity input, or the stored main branch
+  long long ld_other;
+  const float* res_scale;  // [N] BN of the residual (downsample) branch, or null
+  const float* res_shift;
+};
+int gemm_x3s_stats_launch(const capmi_gemm_problem& p, long long lda, int tiles, int grid, hipStream_t s);
+int gemm_x3s_tail_launch(const capmi_gemm_problem& p, long long lda, int tiles, int grid, const X3sTail& e,
+                         bool acc_is_residual, hipStream_t s);
 // conv weight gradients (gemm_x3w.hip): A = dY fp32 k rows, B = fp32 k rows (bmode 1) or the NHWC conv input's
 // implicit im2col (bmode 2), both split in-kernel; grid = tiles x S k-splits (a.kchunk[0] k-tiles each)
 int gemm_x3w_launch(const GemmArgs& a, int bmode, int blocks, hipStream_t s, int terms);  // terms 3 (x3) or 1 (bf16)

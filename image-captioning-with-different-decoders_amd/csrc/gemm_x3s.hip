@@ -46,10 +46,19 @@ __device__ __forceinline__ bf16x4_s cvt4s(float4 v) {
   return r;
 }
 
-template <int NCB, bool PRO>
-__global__ void __launch_bounds__(SNT) __attribute__((amdgpu_waves_per_eu(2)))
-gemm_x3s_kernel(const capmi_gemm_problem P, long long lda, int tiles) {
+// What a tile's accumulators become (x3s_body's EPI): stored with their statistics (the conv itself), the
+// statistics alone (no C at all), or the bottleneck tail -- BN + residual + ReLU -> the block output -- with the
+// accumulator as the main (TAIL) or the residual (TAIL_RES) branch. The three share one tile loop: the same A
+// split, LDS layout, MFMA order and tile-to-workgroup mapping, hence bit-identical accumulators, so a train-mode
+// BN can take its statistics from one pass and be applied to the product recomputed by another, and the raw
+// conv output is never written or read back.
+enum { X3S_STORE = 0, X3S_STATS = 1, X3S_TAIL = 2, X3S_TAIL_RES = 3 };
+
+template <int NCB, bool PRO, int EPI>
+__device__ __forceinline__ void x3s_body(const capmi_gemm_problem& P, long long lda, int tiles, const X3sTail& E) {
+  constexpr bool kTail = EPI == X3S_TAIL || EPI == X3S_TAIL_RES;
   __shared__ __attribute__((aligned(16))) __bf16 As[2][3][SBM * SKD];
+  __shared__ float Bn[4][64 * NCB];  // tail only: scale, shift, res_scale, res_shift of the N columns
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int rl = lane & 15, c4 = lane >> 4;
   const int M = P.M, N = P.N;
@@ -109,16 +118,58 @@ gemm_x3s_kernel(const capmi_gemm_problem P, long long lda, int tiles) {
     }
   };
 
+  if constexpr (kTail) {  // (read back after the first barrier below)
+    if (tid < 64 * NCB) {
+      Bn[0][tid] = E.scale[tid];
+      Bn[1][tid] = E.shift[tid];
+      if constexpr (EPI == X3S_TAIL_RES) {
+        Bn[2][tid] = E.res_scale[tid];
+        Bn[3][tid] = E.res_shift[tid];
+      }
+    }
+  }
   int t = blockIdx.x;  // (the host launches at most `tiles` workgroups)
   load_a(t);
   store_a(0);
   __syncthreads();
-  const auto rc = rsrc_s(P.C, (unsigned)((long long)M * P.ldc * 4));
+  const auto rc = rsrc_s(P.C, (unsigned)((long long)M * P.ldc * 4));  // (statistics pass: never accessed)
   const unsigned cbo = (unsigned)(wc0 + rl) * 4u;
   float* __restrict__ stats = P.stats;
+  // tail: the `other` values of ONE column block (16 rows of this lane's column) and that column's BN
+  // parameters (from LDS), loaded one block ahead of the block that consumes them (a whole tile's would be 64 more
+  // registers beside the 96 of B and the 64 accumulators). Row 16 rb + r of the lane is k = 16 rb + r rows below
+  // its first (tile row + 4 c4): byte offset base + k ld, rebuilt per access from the block's base (kept opaque
+  // per block, or the 2 x 16 offsets would be held across the whole epilogue); rows past M are at or beyond
+  // M ld 4 bytes, the size of both descriptors, so they are neither loaded nor stored (the host bounds
+  // (M + 63) ld 4 below 2^32: no wrap)
+  float ov[16], bnp[4];
+  const auto ro = rsrc_s(E.other, (unsigned)((long long)M * E.ld_other * 4));
+  const unsigned ldo4 = (unsigned)E.ld_other * 4u, ldc4 = (unsigned)P.ldc * 4u;
+  unsigned obase = 0, cbase = 0;
+  auto load_o = [&](int cb) {
+    const int n = wc0 + rl + 16 * cb;
+    bnp[0] = Bn[0][n];
+    bnp[1] = Bn[1][n];
+    if constexpr (EPI == X3S_TAIL_RES) {
+      bnp[2] = Bn[2][n];
+      bnp[3] = Bn[3][n];
+    }
+    unsigned b = obase + 64u * cb;
+    asm volatile("" : "+v"(b));
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+      ov[k] = __uint_as_float(
+          __builtin_amdgcn_raw_buffer_load_b32(ro, b + (unsigned)(16 * (k >> 2) + (k & 3)) * ldo4, 0, 0));
+  };
   int buf = 0;
   for (; t < tiles; t += gridDim.x) {
     load_a(t + gridDim.x);  // past the last tile: zeros, never stored
+    if constexpr (kTail) {
+      const unsigned row0 = (unsigned)(t * SBM + 4 * c4);
+      obase = row0 * ldo4 + cbo;
+      cbase = row0 * ldc4 + cbo;
+      load_o(0);  // in flight across the tile's MFMAs
+    }
     __builtin_amdgcn_sched_barrier(0);
     f32x4_s acc[4][NCB];
 #pragma unroll
@@ -146,34 +197,62 @@ gemm_x3s_kernel(const capmi_gemm_problem P, long long lda, int tiles) {
       }
     }
     // epilogue: lane holds rows 16 rb + 4 c4 + r of column 16 cb + rl of the wave's block
-    unsigned roff[4][4];
+    if constexpr (kTail) {
 #pragma unroll
-    for (int rb = 0; rb < 4; ++rb)
+      for (int cb = 0; cb < NCB; ++cb) {
+        // bn_add_relu_kernel's operations in its order: explicit fma, one add, max
+        unsigned b = cbase + 64u * cb;
+        asm volatile("" : "+v"(b));
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = t * SBM + 16 * rb + 4 * c4 + r;
-        roff[rb][r] = row < M ? (unsigned)row * (unsigned)P.ldc * 4u : kOOBs;
+        for (int rb = 0; rb < 4; ++rb)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float v = acc[rb][cb][r], x = ov[4 * rb + r];
+            float o;
+            if constexpr (EPI == X3S_TAIL)
+              o = fmaxf(fmaf(v, bnp[0], bnp[1]) + x, 0.f);
+            else {
+              float rr = fmaf(v, bnp[2], bnp[3]);
+              asm("" : "+v"(rr));  // (keeps the two fmas scalar: packed, they want (x, v) in register pairs -- copies)
+              o = fmaxf(fmaf(x, bnp[0], bnp[1]) + rr, 0.f);
+            }
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o), rc, b + (unsigned)(16 * rb + r) * ldc4, 0, 0);
+          }
+        if (cb + 1 < NCB) load_o(cb + 1);  // (ov is consumed: the next block's loads follow these stores)
+      }
+    } else {
+      unsigned roff[4][4];
+      if constexpr (EPI == X3S_STORE) {
+#pragma unroll
+        for (int rb = 0; rb < 4; ++rb)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int row = t * SBM + 16 * rb + 4 * c4 + r;
+            roff[rb][r] = row < M ? (unsigned)row * (unsigned)P.ldc * 4u : kOOBs;
+          }
       }
 #pragma unroll
-    for (int cb = 0; cb < NCB; ++cb) {
-      float s = 0.f, q = 0.f;
+      for (int cb = 0; cb < NCB; ++cb) {
+        float s = 0.f, q = 0.f;
 #pragma unroll
-      for (int rb = 0; rb < 4; ++rb)
+        for (int rb = 0; rb < 4; ++rb)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float v = acc[rb][cb][r];
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rc, roff[rb][r] + cbo + 64u * cb, 0, 0);
-          s += v;
-          q = fmaf(v, v, q);
-        }
-      if (stats != nullptr) {
-        s += __shfl_xor(s, 16, 64);
-        q += __shfl_xor(q, 16, 64);
-        s += __shfl_xor(s, 32, 64);
-        q += __shfl_xor(q, 32, 64);
-        if (c4 == 0) {
-          const long long o = ((long long)t * N + wc0 + 16 * cb + rl) * 2;
-          *reinterpret_cast<float2*>(stats + o) = make_float2(s, q);
+          for (int r = 0; r < 4; ++r) {
+            const float v = acc[rb][cb][r];
+            if constexpr (EPI == X3S_STORE)
+              __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rc, roff[rb][r] + cbo + 64u * cb, 0, 0);
+            s += v;
+            q = fmaf(v, v, q);
+          }
+        if (stats != nullptr) {
+          s += __shfl_xor(s, 16, 64);
+          q += __shfl_xor(q, 16, 64);
+          s += __shfl_xor(s, 32, 64);
+          q += __shfl_xor(q, 32, 64);
+          if (c4 == 0) {
+            const long long o = ((long long)t * N + wc0 + 16 * cb + rl) * 2;
+            *reinterpret_cast<float2*>(stats + o) = make_float2(s, q);
+          }
         }
       }
     }
@@ -181,6 +260,26 @@ gemm_x3s_kernel(const capmi_gemm_problem P, long long lda, int tiles) {
     __syncthreads();
     buf ^= 1;
   }
+}
+
+template <int NCB, bool PRO>
+__global__ void __launch_bounds__(SNT) __attribute__((amdgpu_waves_per_eu(2)))
+gemm_x3s_kernel(const capmi_gemm_problem P, long long lda, int tiles) {
+  x3s_body<NCB, PRO, X3S_STORE>(P, lda, tiles, X3sTail{});
+}
+
+// the statistics pass: stats[tile][N][2] as gemm_x3s_kernel writes them, bit for bit; no C
+template <int NCB, bool PRO>
+__global__ void __launch_bounds__(SNT) __attribute__((amdgpu_waves_per_eu(2)))
+gemm_x3s_stats_kernel(const capmi_gemm_problem P, long long lda, int tiles) {
+  x3s_body<NCB, PRO, X3S_STATS>(P, lda, tiles, X3sTail{});
+}
+
+// the tail pass: C = relu(bn(acc) + other) (RES false) or relu(bn(other) + res_bn(acc)) (RES true); no statistics
+template <int NCB, bool PRO, bool RES>
+__global__ void __launch_bounds__(SNT) __attribute__((amdgpu_waves_per_eu(2)))
+gemm_x3s_tail_kernel(const capmi_gemm_problem P, long long lda, int tiles, const X3sTail E) {
+  x3s_body<NCB, PRO, RES ? X3S_TAIL_RES : X3S_TAIL>(P, lda, tiles, E);
 }
 
 }  // namespace
@@ -205,6 +304,37 @@ int gemm_x3s_launch(const capmi_gemm_problem& p, long long lda, int tiles, int g
   else
     return CAPMI_EINVAL;
 #undef X3S_GO
+  CAPMI_LAUNCH_CHECK();
+  return 0;
+}
+
+int gemm_x3s_stats_launch(const capmi_gemm_problem& p, long long lda, int tiles, int grid, hipStream_t s) {
+  CAPMI_REQUIRE(grid >= 1 && grid <= tiles && p.N == 256 && p.stats != nullptr, CAPMI_EINVAL);
+  const dim3 g(grid), b(SNT);
+  if (p.in_scale != nullptr)
+    CAPMI_KLAUNCH((gemm_x3s_stats_kernel<4, true>), g, b, 0, s, p, lda, tiles);
+  else
+    CAPMI_KLAUNCH((gemm_x3s_stats_kernel<4, false>), g, b, 0, s, p, lda, tiles);
+  CAPMI_LAUNCH_CHECK();
+  return 0;
+}
+
+int gemm_x3s_tail_launch(const capmi_gemm_problem& p, long long lda, int tiles, int grid, const X3sTail& e,
+                         bool acc_is_residual, hipStream_t s) {
+  CAPMI_REQUIRE(grid >= 1 && grid <= tiles && p.N == 256, CAPMI_EINVAL);
+  const bool pro = p.in_scale != nullptr;
+  const dim3 g(grid), b(SNT);
+  if (acc_is_residual) {
+    if (pro)
+      CAPMI_KLAUNCH((gemm_x3s_tail_kernel<4, true, true>), g, b, 0, s, p, lda, tiles, e);
+    else
+      CAPMI_KLAUNCH((gemm_x3s_tail_kernel<4, false, true>), g, b, 0, s, p, lda, tiles, e);
+  } else {
+    if (pro)
+      CAPMI_KLAUNCH((gemm_x3s_tail_kernel<4, true, false>), g, b, 0, s, p, lda, tiles, e);
+    else
+      CAPMI_KLAUNCH((gemm_x3s_tail_kernel<4, false, false>), g, b, 0, s, p, lda, tiles, e);
+  }
   CAPMI_LAUNCH_CHECK();
   return 0;
 }

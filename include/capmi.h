@@ -196,6 +196,22 @@ int capmi_gemm_sk_plan(const capmi_gemm_problem* problem, int amode, int bmode, 
  * without return type and parameters, as rocprofv3 lists it) into out[n]: what a plan query's name must equal.
  * Needs the HIP runtime's code-object registry (a GPU process). */
 int capmi_last_launch_name(char* out, int n);
+/* The CAPMI_GEMM_X3S product computed twice instead of stored and re-read (layer1's N = 256 convs under a
+ * train-mode BatchNorm + residual + ReLU; additive entry points, ABI unchanged). `problem` / `amode` are a
+ * CAPMI_GEMM_X3S problem (validated as capmi_gemm_sk_ex validates it) with N == 256.
+ * capmi_gemm_x3s_stats: the statistics pass -- problem->stats ([ceil(M/64)][N][2], required) receives bit for
+ * bit what capmi_gemm_sk_ex(CAPMI_GEMM_X3S) writes there; C is neither read nor written and may be NULL. */
+int capmi_gemm_x3s_stats(const capmi_gemm_problem* problem, int amode, void* stream);
+/* capmi_gemm_x3s_tail: the tail pass -- the same accumulators acc[m][n], then with o = other[m*ld_other + n]
+ *   acc_is_residual == 0: C[m][n] = max(fma(acc, scale[n], shift[n]) + o, 0)          (res_scale, res_shift NULL)
+ *   acc_is_residual == 1: C[m][n] = max(fma(o, scale[n], shift[n]) + fma(acc, res_scale[n], res_shift[n]), 0)
+ * i.e. capmi_bn_add_relu's operations in its order, on the product instead of a stored y (0: the product is the
+ * main branch and `other` the identity; 1: the product is the downsample branch and `other` the stored main
+ * branch). other 16-B aligned, ld_other >= N, M*ld_other*4 < 2^31; rows past M are neither loaded nor stored;
+ * problem->stats is ignored (no statistics are written). */
+int capmi_gemm_x3s_tail(const capmi_gemm_problem* problem, int amode, const float* scale, const float* shift,
+                        const float* other, long long ld_other, const float* res_scale, const float* res_shift,
+                        int acc_is_residual, void* stream);
 
 /* sum of S partial slabs: out[r][c] = sum_s in[s*slab + r*ld_in + c] (+ bias[c]); rows x cols */
 int capmi_splitk_reduce(const float* in, int S, long long slab, int rows, int cols, long long ld_in,
