@@ -598,6 +598,22 @@ bool sk_off() {
   }();
   return off;
 }
+// Attach the stream-K workspace (the flags, then one parked-partial slot per worker) to a launch of `total` output
+// tiles of `nkt` k-tiles each on `slots` resident workgroups. hybrid: with more than two rounds of tiles, all but the
+// last 1-2 rounds' worth run whole before the stream-K part. What a null workspace means is the caller's rule.
+int sk_attach(GemmArgs& a, long long total, int nkt, long long slots, bool hybrid, void* workspace,
+              long long ws_bytes) {
+  CAPMI_REQUIRE(aligned16(workspace), CAPMI_EINVAL);
+  CAPMI_REQUIRE(ws_bytes >= capmi_gemm_workspace_bytes(), CAPMI_ERANGE);
+  a.sk_nkt = nkt;
+  a.sk_dp_tiles = hybrid && sk_hybrid() && total >= 2 * slots ? (int)((total / slots - 1) * slots) : 0;
+  a.sk_units = (total - a.sk_dp_tiles) * a.sk_nkt;
+  a.sk_workers = (int)std::min<long long>(slots, a.sk_units);
+  a.sk_groups = sk_xcd_groups() && a.sk_workers % 8 == 0 && total >= 64 ? 8 : 1;
+  a.sk_flags = static_cast<int*>(workspace);
+  a.sk_part = reinterpret_cast<float*>(static_cast<char*>(workspace) + sk_flag_bytes(cu_count()));
+  return 0;
+}
 // the three-term conv weight gradients keep the fp32 wgrad tile rule (128x128 / 128x64, one workgroup per
 // CU): fine-tune config 1633 -> 1647 img/s against 64x64 (fewer re-reads of dY and the im2col rows).
 // CAPMI_X3_WGRAD_WIDE=0: 64x64 (A/B measurement)
@@ -884,18 +900,8 @@ int gemm_bf16_io(const capmi_gemm_problem* prob, int amode, int bmode, int tile,
   if (p.ldc % 8 != 0 || !aligned16(p.C)) a.plain_epi = 0;  // (its 16-B row-chunk stores)
   const long long total = pl.total;
   a.tiles_begin[1] = (int)total;
-  const int cus = cu_count();
-  const long long slots = (long long)sk_cus() * 2;
-  const int nkt = p.K / 64;
   if (!pl.sk) return gemm_bf16_launch(a, amode, bm, bn, (int)total, s, pl.stages);
-  CAPMI_REQUIRE(aligned16(workspace), CAPMI_EINVAL);
-  CAPMI_REQUIRE(ws_bytes >= capmi_gemm_workspace_bytes(), CAPMI_ERANGE);
-  a.sk_nkt = nkt;
-  a.sk_units = total * nkt;
-  a.sk_workers = (int)std::min<long long>(slots, a.sk_units);
-  a.sk_groups = sk_xcd_groups() && a.sk_workers % 8 == 0 && total >= 64 ? 8 : 1;
-  a.sk_flags = static_cast<int*>(workspace);
-  a.sk_part = reinterpret_cast<float*>(static_cast<char*>(workspace) + sk_flag_bytes(cus));
+  if (const int e = sk_attach(a, total, p.K / 64, (long long)sk_cus() * 2, false, workspace, ws_bytes)) return e;
   return gemm_bf16_launch(a, amode, bm, bn, a.sk_workers, s, 2);
 }
 }  // namespace
@@ -1027,17 +1033,7 @@ int gemm_x3p(const capmi_gemm_problem* prob, int amode, int bmode, void* workspa
   if (rc) return rc;
   if (prob->M == 0) return 0;
   if (!sk || workspace == nullptr) return gemm_x3p_launch(a, amode, bk, (int)total, s);
-  CAPMI_REQUIRE(aligned16(workspace), CAPMI_EINVAL);
-  CAPMI_REQUIRE(ws_bytes >= capmi_gemm_workspace_bytes(), CAPMI_ERANGE);
-  const int cus = cu_count();
-  const long long slots = sk_cus();
-  a.sk_nkt = prob->K / bk;  // k-tiles of the x3p kernel
-  a.sk_dp_tiles = sk_hybrid() && total >= 2 * slots ? (int)((total / slots - 1) * slots) : 0;
-  a.sk_units = (total - a.sk_dp_tiles) * a.sk_nkt;
-  a.sk_workers = (int)std::min<long long>(slots, a.sk_units);
-  a.sk_groups = sk_xcd_groups() && a.sk_workers % 8 == 0 && total >= 64 ? 8 : 1;
-  a.sk_flags = static_cast<int*>(workspace);
-  a.sk_part = reinterpret_cast<float*>(static_cast<char*>(workspace) + sk_flag_bytes(cus));
+  if (const int e = sk_attach(a, total, prob->K / bk, sk_cus(), true, workspace, ws_bytes)) return e;
   return gemm_x3p_launch(a, amode, bk, a.sk_workers, s);
 }
 
@@ -1108,17 +1104,7 @@ int gemm_x3d(const capmi_gemm_problem* prob, int amode, int bmode, void* workspa
   if (rc) return rc;
   if (prob->M == 0) return 0;
   if (!sk || workspace == nullptr) return gemm_x3d_launch(a, amode, (int)total, s);
-  CAPMI_REQUIRE(aligned16(workspace), CAPMI_EINVAL);
-  CAPMI_REQUIRE(ws_bytes >= capmi_gemm_workspace_bytes(), CAPMI_ERANGE);
-  const int cus = cu_count();
-  const long long slots = sk_cus();
-  a.sk_nkt = prob->K / 32;
-  a.sk_dp_tiles = sk_hybrid() && total >= 2 * slots ? (int)((total / slots - 1) * slots) : 0;
-  a.sk_units = (total - a.sk_dp_tiles) * a.sk_nkt;
-  a.sk_workers = (int)std::min<long long>(slots, a.sk_units);
-  a.sk_groups = sk_xcd_groups() && a.sk_workers % 8 == 0 && total >= 64 ? 8 : 1;
-  a.sk_flags = static_cast<int*>(workspace);
-  a.sk_part = reinterpret_cast<float*>(static_cast<char*>(workspace) + sk_flag_bytes(cus));
+  if (const int e = sk_attach(a, total, prob->K / 32, sk_cus(), true, workspace, ws_bytes)) return e;
   return gemm_x3d_launch(a, amode, a.sk_workers, s);
 }
 
@@ -1286,17 +1272,7 @@ int gemm_x3(const capmi_gemm_problem* prob, int amode, int bmode, int tile, void
   if (rc) return rc;
   if (prob->M == 0) return 0;
   if (!sk || workspace == nullptr) return gemm_x3_launch(a, amode, bn, (int)total, s);
-  CAPMI_REQUIRE(aligned16(workspace), CAPMI_EINVAL);
-  CAPMI_REQUIRE(ws_bytes >= capmi_gemm_workspace_bytes(), CAPMI_ERANGE);
-  const int cus = cu_count();
-  const long long slots = sk_cus();
-  a.sk_nkt = prob->K / 32;
-  a.sk_dp_tiles = sk_hybrid() && total >= 2 * slots ? (int)((total / slots - 1) * slots) : 0;
-  a.sk_units = (total - a.sk_dp_tiles) * a.sk_nkt;
-  a.sk_workers = (int)std::min<long long>(slots, a.sk_units);
-  a.sk_groups = sk_xcd_groups() && a.sk_workers % 8 == 0 && total >= 64 ? 8 : 1;
-  a.sk_flags = static_cast<int*>(workspace);
-  a.sk_part = reinterpret_cast<float*>(static_cast<char*>(workspace) + sk_flag_bytes(cus));
+  if (const int e = sk_attach(a, total, prob->K / 32, sk_cus(), true, workspace, ws_bytes)) return e;
   return gemm_x3_launch(a, amode, bn, a.sk_workers, s);
 }
 }  // namespace
@@ -1363,19 +1339,11 @@ extern "C" int capmi_gemm_sk_ex(const capmi_gemm_problem* prob, int amode, int b
     return terms ? gemm_nt_launch(g.a, amode, bmode, g.bm, g.bn, (int)g.total, s, terms)
                  : gemm_launch_dp(g, amode, bmode, s);
   }
-  CAPMI_REQUIRE(workspace != nullptr && aligned16(workspace), CAPMI_EINVAL);
-  CAPMI_REQUIRE(ws_bytes >= capmi_gemm_workspace_bytes(), CAPMI_ERANGE);
-  const int cus = cu_count();
+  CAPMI_REQUIRE(workspace != nullptr, CAPMI_EINVAL);
   const long long slots = (long long)sk_cus() * (g.nt == 512 ? 1 : gemm_nt_wg_per_cu(g.bm, g.bn, terms));
   GemmArgs& a = g.a;
-  a.sk_nkt = (prob->K + 31) / 32;
-  // hybrid: with more than two rounds of tiles, all but the last 1-2 rounds' worth run whole
-  a.sk_dp_tiles = sk_hybrid() && g.total >= 2 * slots ? (int)((g.total / slots - 1) * slots) : 0;
-  a.sk_units = (g.total - a.sk_dp_tiles) * a.sk_nkt;
-  a.sk_workers = (int)std::min<long long>(slots, a.sk_units);
-  a.sk_groups = sk_xcd_groups() && a.sk_workers % 8 == 0 && g.total >= 64 ? 8 : 1;
-  a.sk_flags = static_cast<int*>(workspace);
-  a.sk_part = reinterpret_cast<float*>(static_cast<char*>(workspace) + sk_flag_bytes(cus));
+  rc = sk_attach(a, g.total, (prob->K + 31) / 32, slots, true, workspace, ws_bytes);
+  if (rc) return rc;
   return gemm_nt_launch(a, amode, bmode, g.bm, g.bn, a.sk_workers, s, terms, g.nt);
 }
 

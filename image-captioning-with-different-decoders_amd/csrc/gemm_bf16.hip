@@ -18,24 +18,12 @@
 //   * tiles 128x128 (wave 64x64: 4 MFMAs per 4 ds_read_b128) or 128x64;
 //   * round 5: for K <= 256 a one-stage 128x64 form at four workgroups per CU (ST = 1 below), and the
 //     store-only epilogue leaves through LDS as 16-B row chunks.
-#include "gemm_args.h"
+#include "x3_common.h"
 
 namespace {
 
 constexpr int BKH = 64;      // k per tile (bf16 elements)
 constexpr int SBH = BKH + 8;  // LDS row stride (elements)
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-constexpr unsigned kOOB = 0x80000000u;  // buffer offset past every operand: the load returns 0
-constexpr int kSc1h = 16;
-#ifndef BF16_SKIP  // timing-only builds (wrong results): 1 no C stores, 2 no MFMAs, 4 no operand loads
-#define BF16_SKIP 0
-#endif
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_of(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-
 __device__ __forceinline__ unsigned short bf16_bits(float x) {
   return __builtin_bit_cast(unsigned short, (__bf16)x);  // RNE
 }
@@ -100,8 +88,8 @@ gemm_bf16_kernel(const GemmArgs args) {
   const capmi_gemm_problem& P0 = args.p[0];
   const unsigned a_bytes = AMODE == 2 ? (unsigned)((long long)P0.cN * P0.cH * P0.cW * P0.cCin * 2)
                                       : (unsigned)((long long)P0.M * P0.lda * 2);
-  const auto ra = rsrc_of(P0.A, a_bytes);
-  const auto rb = rsrc_of(P0.B, (unsigned)((long long)P0.N * P0.ldb * 2));
+  const auto ra = buf_rsrc(P0.A, a_bytes);
+  const auto rb = buf_rsrc(P0.B, (unsigned)((long long)P0.N * P0.ldb * 2));
   unsigned a_off[NA];  // dense: byte offset of (row, kc); conv: element offset of the image
   int a_ih0[NA], a_iw0[NA];
   bool a_ok[NA];
@@ -109,7 +97,7 @@ gemm_bf16_kernel(const GemmArgs args) {
   int c_ci = 0, c_kh = 0, c_kw = 0;  // conv k walk, advanced BKH per k-tile
   int t_lo = 0, t_hi = 0;             // k range of the current tile
   struct Stage {
-    u32x4_t ra[NA], rb[NB];
+    u32x4 ra[NA], rb[NB];
   };
   Stage s0, s1;
 
@@ -152,7 +140,7 @@ gemm_bf16_kernel(const GemmArgs args) {
     if (AMODE == 0) {
 #pragma unroll
       for (int i = 0; i < NA; ++i)
-        st.ra[i] = __builtin_amdgcn_raw_buffer_load_b128(ra, kok && !(BF16_SKIP & 4) ? a_off[i] + (unsigned)k * 2 : kOOB, 0, 0);
+        st.ra[i] = __builtin_amdgcn_raw_buffer_load_b128(ra, kok ? a_off[i] + (unsigned)k * 2 : kOOB, 0, 0);
     } else {
       const int cH = P0.cH, cW = P0.cW, cCin = P0.cCin;
 #pragma unroll
@@ -160,7 +148,7 @@ gemm_bf16_kernel(const GemmArgs args) {
         const int ih = a_ih0[i] + c_kh, iw = a_iw0[i] + c_kw;
         const bool ok = a_ok[i] && kok && (unsigned)ih < (unsigned)cH && (unsigned)iw < (unsigned)cW;
         const unsigned off = ((a_off[i] + (unsigned)(ih * cW + iw)) * (unsigned)cCin + (unsigned)(c_ci + kc)) * 2u;
-        st.ra[i] = __builtin_amdgcn_raw_buffer_load_b128(ra, ok && !(BF16_SKIP & 4) ? off : kOOB, 0, 0);
+        st.ra[i] = __builtin_amdgcn_raw_buffer_load_b128(ra, ok ? off : kOOB, 0, 0);
       }
       c_ci += BKH;
       if (c_ci >= cCin) {
@@ -173,14 +161,14 @@ gemm_bf16_kernel(const GemmArgs args) {
     }
 #pragma unroll
     for (int i = 0; i < NB; ++i)
-      st.rb[i] = __builtin_amdgcn_raw_buffer_load_b128(rb, kok && !(BF16_SKIP & 4) ? b_off[i] + (unsigned)k * 2 : kOOB, 0, 0);
+      st.rb[i] = __builtin_amdgcn_raw_buffer_load_b128(rb, kok ? b_off[i] + (unsigned)k * 2 : kOOB, 0, 0);
   };
   // DMA ring: k-tile kt of the current tile into LDS stage buf, NA + NB wave-instructions per wave whatever kt is
   // (past the k range every lane reads zeros), so the per-k-tile vmcnt count is a constant
   const int wdu = __builtin_amdgcn_readfirstlane(wid);  // wave-uniform: the LDS-DMA bases in SGPRs
   auto issue = [&](int kt, int buf) {
     const int k = t_lo + kt * BKH;
-    const bool kok = k < t_hi && !(BF16_SKIP & 4);
+    const bool kok = k < t_hi;
     unsigned offa[4];
     if (AMODE == 0) {
 #pragma unroll
@@ -212,11 +200,11 @@ gemm_bf16_kernel(const GemmArgs args) {
     for (int i = 0; i < NB; ++i) offb[i] = kok ? b_off[i] + (unsigned)k * 2 : kOOB;
 #pragma unroll
     for (int i = 0; i < NA; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (__attribute__((address_space(3))) void*)(ab + i * NT * 8), 16,
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_ptr_t)(ab + i * NT * 8), 16,
                                                offa[i], 0, 0, 0);
 #pragma unroll
     for (int i = 0; i < NB; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (__attribute__((address_space(3))) void*)(bb + i * NT * 8), 16,
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (lds_ptr_t)(bb + i * NT * 8), 16,
                                                offb[i], 0, 0, 0);
   };
   // the first k-tiles of a tile into the register stages (the DMA ring issues its own in the k-loop)
@@ -228,10 +216,10 @@ gemm_bf16_kernel(const GemmArgs args) {
   };
   auto store_tile = [&](const Stage& st, int buf) {
 #pragma unroll
-    for (int i = 0; i < NA; ++i) *reinterpret_cast<u32x4_t*>(&As[buf * BM * SB + ((tid + i * NT) >> 3) * SB + kc]) = st.ra[i];
+    for (int i = 0; i < NA; ++i) *reinterpret_cast<u32x4*>(&As[buf * BM * SB + ((tid + i * NT) >> 3) * SB + kc]) = st.ra[i];
 #pragma unroll
     for (int i = 0; i < NB; ++i)
-      *reinterpret_cast<u32x4_t*>(&Bs[buf * BN * SB + ((tid + i * NT) >> 3) * SB + kc]) = st.rb[i];
+      *reinterpret_cast<u32x4*>(&Bs[buf * BN * SB + ((tid + i * NT) >> 3) * SB + kc]) = st.rb[i];
   };
   const int dsw = (lr >> 1) & 7;  // DMA ring: the swizzle of this lane's read rows (wm0 / wn0 + lr + 32 i)
   auto compute = [&](int buf) {
@@ -239,20 +227,17 @@ gemm_bf16_kernel(const GemmArgs args) {
     const __bf16* Bh = &Bs[buf * BN * SB + (wn0 + lr) * SB + (DMA ? 0 : 8 * lh)];
 #pragma unroll
     for (int g = 0; g < BKH / 16; ++g) {
-      bf16x8_t a[TM], b[TN];
+      bf16x8 a[TM], b[TN];
       const int ko = DMA ? ((2 * g + lh) ^ dsw) * 8 : 16 * g;
 #pragma unroll
-      for (int i = 0; i < TM; ++i) a[i] = *reinterpret_cast<const bf16x8_t*>(Ah + 32 * i * SB + ko);
+      for (int i = 0; i < TM; ++i) a[i] = *reinterpret_cast<const bf16x8*>(Ah + 32 * i * SB + ko);
 #pragma unroll
-      for (int j = 0; j < TN; ++j) b[j] = *reinterpret_cast<const bf16x8_t*>(Bh + 32 * j * SB + ko);
+      for (int j = 0; j < TN; ++j) b[j] = *reinterpret_cast<const bf16x8*>(Bh + 32 * j * SB + ko);
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j)
-          if (BF16_SKIP & 2)
-            acc[i][j][0] += (float)a[i][0] * (float)b[j][1];
-          else
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
     }
   };
   auto kstep = [&](Stage& ld, const Stage& sv, int kt) {
@@ -338,14 +323,13 @@ gemm_bf16_kernel(const GemmArgs args) {
           }
       }
       __syncthreads();
-      const auto rc = rsrc_of(C, (unsigned)((long long)M * ldc * 2));
+      const auto rc = buf_rsrc(C, (unsigned)((long long)M * ldc * 2));
       constexpr int CPR = BN / 8;  // 16-B chunks per row
 #pragma unroll
       for (int q = 0; q < BM * CPR / NT; ++q) {
         const int e = q * NT + tid, row = e / CPR, ch = e % CPR;
-        const u32x4_t v = *reinterpret_cast<const u32x4_t*>(E + row * ES + ch * 8);
-        if (!(BF16_SKIP & 1))
-          __builtin_amdgcn_raw_buffer_store_b128(v, rc, (unsigned)(((long long)(m0 + row) * ldc + n0 + ch * 8) * 2), 0, 0);
+        const u32x4 v = *reinterpret_cast<const u32x4*>(E + row * ES + ch * 8);
+        __builtin_amdgcn_raw_buffer_store_b128(v, rc, (unsigned)(((long long)(m0 + row) * ldc + n0 + ch * 8) * 2), 0, 0);
       }
       __syncthreads();  // (the next k-loop's first LDS stores overwrite the staging tile)
     } else
@@ -431,12 +415,12 @@ gemm_bf16_kernel(const GemmArgs args) {
         for (int j = 0; j < TN; ++j)
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            u32x4_t v;
+            u32x4 v;
             v.x = __float_as_uint(acc[i][j][4 * q + 0]);
             v.y = __float_as_uint(acc[i][j][4 * q + 1]);
             v.z = __float_as_uint(acc[i][j][4 * q + 2]);
             v.w = __float_as_uint(acc[i][j][4 * q + 3]);
-            __builtin_amdgcn_raw_buffer_store_b128(v, rs, (((i * TN + j) * 4 + q) * NT + tid) * 16, 0, kSc1h);
+            __builtin_amdgcn_raw_buffer_store_b128(v, rs, (((i * TN + j) * 4 + q) * NT + tid) * 16, 0, kSc1);
           }
       sk_publish(flags + blockIdx.x, tid);
       continue;
@@ -452,7 +436,7 @@ gemm_bf16_kernel(const GemmArgs args) {
           for (int j = 0; j < TN; ++j)
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-              const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rs, (((i * TN + j) * 4 + q) * NT + tid) * 16, 0, kSc1h);
+              const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (((i * TN + j) * 4 + q) * NT + tid) * 16, 0, kSc1);
               acc[i][j][4 * q + 0] += __uint_as_float(v.x);
               acc[i][j][4 * q + 1] += __uint_as_float(v.y);
               acc[i][j][4 * q + 2] += __uint_as_float(v.z);

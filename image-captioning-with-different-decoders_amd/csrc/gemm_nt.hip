@@ -23,15 +23,12 @@
 //     input read as k rows (k = output pixel, n = (kh, kw, ci)), staged like BMODE 1; the
 //     optional BN-apply+ReLU prologue then acts on B (the conv's input is relu(bn(y_prev))).
 // Numerics: unchanged (exact fp32 fmaf chains, different k order than any CPU library).
-#include "gemm_args.h"
+#include "x3_common.h"
 
 namespace {
 
 constexpr int BK2 = 32;
 constexpr int S2 = BK2 + 4;  // LDS row stride in floats
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-constexpr int kSc1 = 16;  // buffer-op aux bit: sc1 (write-through store / L1-bypassing load)
 
 // buffer descriptor of one parked-partial slot (wave-uniform inputs only)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t slot_rsrc(float* base, long long off_floats) {
@@ -58,8 +55,6 @@ constexpr int kWavesPerEu = (BM == 64 && BN == 64) ? 4 : 2;
 // 16 lanes x 16 B at stride 80 B touch 64 distinct banks. Accumulation stays fp32; the
 // epilogue, BN statistics and stream-K hand-off are the fp32 kernel's.
 constexpr int SB = BK2 + 8;  // bf16 LDS row stride (elements)
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 
 // the exact split of gemm_x3.hip: t0 = RNE(x), t1 = RNE(x - t0), t2 = x - t0 - t1 (exact in bf16)

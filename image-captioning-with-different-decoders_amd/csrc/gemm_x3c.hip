@@ -17,7 +17,7 @@
 // k order, products and accumulator order are those of the x3p conv path (one workgroup per tile, 32-deep
 // k-tiles) on the same split planes (tests/test_gpu_x3.py::test_x3c_direct_conv).
 // 512 threads = 8 waves as 4 (64-row slices) x 2 (32 output channels); store-only epilogue.
-#include "gemm_args.h"
+#include "x3_common.h"
 
 namespace {
 
@@ -31,15 +31,6 @@ constexpr int CB_PLANE = CBN * 64;    // the weight's 64 x 32 tap block, per pla
 constexpr int CB_BUF = 3 * CB_PLANE;  // 12 KiB
 constexpr int CB_NBUF = 3;            // weight ring: the DMA runs two taps ahead
 constexpr int CPF = (CPOS * 8 + 511) / 512;  // float4 loads per thread to stage one slice of the band
-typedef unsigned u32x4_c __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8_c __attribute__((ext_vector_type(8)));
-typedef float f32x4_c __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_c;
-constexpr unsigned kOOBc = 0x80000000u;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_c(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
 // 16-B chunk c of staged position q sits in slot c ^ (2 ((q >> 2) & 1)). A fragment read's 16 lanes take 16
 // consecutive positions starting ANYWHERE (the tap shift (kh - 1) (W + 2) + kw - 1 moves them), in
 // ds_read_b128's lane groups {0-3, 12-15, 20-27} ... (MI355X_MICROARCH.md, LDS) with two chunks per group;
@@ -86,11 +77,11 @@ gemm_x3c_kernel(const capmi_gemm_problem P) {
   const int rmin = prow(p0) - 1;                                 // first staged padded row
   const int npos = (prow(min(p0 + CBM, M) - 1) + 2 - rmin) * Wp;  // staged positions (<= CPOS: host)
 
-  const auto rx = rsrc_c(P.A, (unsigned)((long long)rows_all * W * Cin * 4));
-  const auto rb = rsrc_c(P.B, (unsigned)(3LL * CBN * P.ldb * 2));
+  const auto rx = buf_rsrc(P.A, (unsigned)((long long)rows_all * W * Cin * 4));
+  const auto rb = buf_rsrc(P.B, (unsigned)(3LL * CBN * P.ldb * 2));
   const unsigned ss_bytes = PRO ? (unsigned)(Cin * 4) : 0u;
-  const auto rsc = rsrc_c(PRO ? (const void*)P.in_scale : P.B, ss_bytes);
-  const auto rsh = rsrc_c(PRO ? (const void*)P.in_shift : P.B, ss_bytes);
+  const auto rsc = buf_rsrc(PRO ? (const void*)P.in_scale : P.B, ss_bytes);
+  const auto rsh = buf_rsrc(PRO ? (const void*)P.in_shift : P.B, ss_bytes);
 
   // this lane's fragment pixels: rows wm0 + 16 i + (lane & 15) of the tile, chunk lane >> 4; their centre
   // positions in the band (a pixel past M reads a position inside the band; its rows are zeroed in the epilogue)
@@ -113,7 +104,7 @@ gemm_x3c_kernel(const capmi_gemm_problem P) {
     const unsigned off = b_base + (unsigned)(kt * 32) * 2u;
 #pragma unroll
     for (int p = 0; p < 3; ++p)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (lds_ptr_c)(Bl + buf * CB_BUF + p * CB_PLANE + wid * 1024), 16,
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (lds_ptr_t)(Bl + buf * CB_BUF + p * CB_PLANE + wid * 1024), 16,
                                                off + p * pB2, 0, 0, 0);
   };
   // input slice s of the band: float4 f = tid + 512 j is position f / 8 = tid / 8 + 64 j, channels 4 (f % 8) .. + 3.
@@ -127,7 +118,7 @@ gemm_x3c_kernel(const capmi_gemm_problem P) {
     const int br = q / Wp, c = q - br * Wp;
     const int R = rmin + br, n = R / Hp, ih = R - n * Hp - 1, iw = c - 1;
     const bool ok = q < npos && (unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W && n < P.cN;
-    soff[j] = ok ? (unsigned)((((long long)(n * H + ih) * W + iw) * Cin + ch8) * 4) : kOOBc;
+    soff[j] = ok ? (unsigned)((((long long)(n * H + ih) * W + iw) * Cin + ch8) * 4) : kOOB;
   }
   float4 pf[CPF];
   float4 pf_sc = make_float4(1.f, 1.f, 1.f, 1.f), pf_sh = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -140,7 +131,7 @@ gemm_x3c_kernel(const capmi_gemm_problem P) {
 #pragma unroll
     for (int j = 0; j < CPF; ++j)
       pf[j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(
-                                             rx, soff[j] == kOOBc ? kOOBc : soff[j] + (unsigned)s * 128u, 0, 0));
+                                             rx, soff[j] == kOOB ? kOOB : soff[j] + (unsigned)s * 128u, 0, 0));
   };
   auto stage_write = [&]() {
 #pragma unroll
@@ -150,7 +141,7 @@ gemm_x3c_kernel(const capmi_gemm_problem P) {
       float4 x = pf[j];
       if (PRO) x = make_float4(fmaxf(fmaf(x.x, pf_sc.x, pf_sh.x), 0.f), fmaxf(fmaf(x.y, pf_sc.y, pf_sh.y), 0.f),
                                fmaxf(fmaf(x.z, pf_sc.z, pf_sh.z), 0.f), fmaxf(fmaf(x.w, pf_sc.w, pf_sh.w), 0.f));
-      if (soff[j] == kOOBc) x = make_float4(0.f, 0.f, 0.f, 0.f);  // padding: zeros AFTER the BN
+      if (soff[j] == kOOB) x = make_float4(0.f, 0.f, 0.f, 0.f);  // padding: zeros AFTER the BN
       unsigned lo[3], hi[3];
       split3_pair(x.x, x.y, lo);
       split3_pair(x.z, x.w, hi);
@@ -161,11 +152,11 @@ gemm_x3c_kernel(const capmi_gemm_problem P) {
     }
   };
 
-  f32x4_c acc[4][2];
+  f32x4 acc[4][2];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4_c{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int nslice = Cin / 32, nkt = nslice * 9;
   // weight ring: tap kt's block in buffer kt % 3, its DMA issued two taps ahead (past the last tap: out of
   // range, zeros into a buffer nobody reads -- so the count of DMA wave-instructions in flight is fixed)
@@ -191,20 +182,20 @@ gemm_x3c_kernel(const capmi_gemm_problem P) {
       const int kh = tap / 3, kw = tap - kh * 3;
       const int dq = (kh - 1) * Wp + (kw - 1);
       const unsigned char* B_ = Bl + buf * CB_BUF;
-      bf16x8_c b[2][3];
+      bf16x8 b[2][3];
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int r = wn0 + 16 * j + r16;
 #pragma unroll
         for (int p = 0; p < 3; ++p)
-          b[j][p] = *reinterpret_cast<const bf16x8_c*>(B_ + p * CB_PLANE + r * 64 + ((c16 ^ bswz(r)) << 4));
+          b[j][p] = *reinterpret_cast<const bf16x8*>(B_ + p * CB_PLANE + r * 64 + ((c16 ^ bswz(r)) << 4));
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int o = apos_off(fq[i] + dq, c16);
-        bf16x8_c a[3];
+        bf16x8 a[3];
 #pragma unroll
-        for (int p = 0; p < 3; ++p) a[p] = *reinterpret_cast<const bf16x8_c*>(Al + p * CA_PLANE + o);
+        for (int p = 0; p < 3; ++p) a[p] = *reinterpret_cast<const bf16x8*>(Al + p * CA_PLANE + o);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {  // per accumulator the six products smallest terms first (x3p's order)
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[j][1], acc[i][j], 0, 0, 0);
@@ -239,7 +230,7 @@ gemm_x3c_kernel(const capmi_gemm_problem P) {
 
   // store-only epilogue (x3p's form): lane l holds rows 4 (l / 16) .. + 3 of column l % 16 of each 16x16 block;
   // rows past M are dropped by the descriptor and zeroed for the statistics
-  const auto rc = rsrc_c(P.C, (unsigned)((long long)M * P.ldc * 4));
+  const auto rc = buf_rsrc(P.C, (unsigned)((long long)M * P.ldc * 4));
   const int cl = lane & 15, rq = lane >> 4;
   unsigned roff[4][4];
 #pragma unroll
@@ -247,7 +238,7 @@ gemm_x3c_kernel(const capmi_gemm_problem P) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int row = p0 + wm0 + 16 * i + 4 * rq + r;
-      roff[i][r] = row < M ? (unsigned)row * (unsigned)P.ldc * 4u : kOOBc;
+      roff[i][r] = row < M ? (unsigned)row * (unsigned)P.ldc * 4u : kOOB;
     }
   float* __restrict__ stats = P.stats;
 #pragma unroll
@@ -259,7 +250,7 @@ gemm_x3c_kernel(const capmi_gemm_problem P) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         // (a row past M read band data: its store is dropped by the descriptor, its value kept out of the sums)
-        const float v = roff[i][r] == kOOBc ? 0.f : acc[i][j][r];
+        const float v = roff[i][r] == kOOB ? 0.f : acc[i][j][r];
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rc, roff[i][r] + cb, 0, 0);
         cs += v;
         cq = fmaf(v, v, cq);

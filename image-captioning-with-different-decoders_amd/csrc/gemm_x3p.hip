@@ -18,7 +18,7 @@
 // deeper prefetch gained: layer3 3x3 101 us vs 85.) Epilogue (fp32 C, alpha/bias/beta/relu,
 // per-64-row BN statistics: a wave's 64 rows are one slice) and the stream-K / hybrid schedule with
 // the write-through hand-off are those of gemm_nt.hip.
-#include "gemm_args.h"
+#include "x3_common.h"
 #include "stamp.h"
 
 STAMP_BUFFER(capmi_x3p_stamps)
@@ -26,16 +26,6 @@ STAMP_BUFFER(capmi_x3p_stamps)
 namespace {
 
 constexpr int PNT = 512;
-typedef unsigned u32x4_p __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8_p __attribute__((ext_vector_type(8)));
-typedef float f32x4_p __attribute__((ext_vector_type(4)));
-constexpr unsigned kOOBp = 0x80000000u;
-constexpr int kSc1p = 16;
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_p(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
 
 // BK = 32: 72 KiB per LDS buffer, one workgroup per CU; BK = 16: 36 KiB, two workgroups per CU (their
 // barriers and DMA waits fall at different times, so one's MFMAs cover the other's stalls)
@@ -55,10 +45,7 @@ struct X3pGeo {
   static constexpr int WPE = PBK == 16 ? 4 : 2;     // waves per SIMD: two workgroups per CU at BK = 16
 };
 
-#ifndef X3P_M16
-#define X3P_M16 1
-#endif
-// MFMA shape (round 3): 32-deep k-tiles run v_mfma_f32_16x16x32_bf16 (X3P_M16, default) -- the same
+// MFMA shape (round 3): 32-deep k-tiles run v_mfma_f32_16x16x32_bf16 -- the same
 // cycles per FLOP as 32x32x16, but MI355X holds a higher clock under a 16x16x32 stream (random data:
 // ~1.12-1.15x the FLOP/s, MI355X_MICROARCH.md 'DVFS give-back' (7)); 16-deep k-tiles keep 32x32x16.
 // LDS chunk swizzle of row r (physical 16-B slot of logical k-chunk c = c ^ swz(r)): for the 16x16x32
@@ -67,7 +54,7 @@ struct X3pGeo {
 // 2g + l / 32) use (r / SWZ) % CPR.
 template <int PBK>
 __device__ __forceinline__ int swz(int r) {
-  if constexpr (PBK == 32 && X3P_M16)
+  if constexpr (PBK == 32)
     return (0x1320 >> (4 * ((r >> 2) & 3))) & 3;
   else
     return (r / X3pGeo<PBK>::SWZ) % X3pGeo<PBK>::CPR;
@@ -76,7 +63,7 @@ __device__ __forceinline__ int swz(int r) {
 // one 16x16x32 bf16 MFMA, c += a . b (round 5 measured the operand-swapped form, whose transposed accumulator
 // blocks the epilogue can store 16 B per lane: 16 rows per store instead of 4 made the epilogue slower, 6.9k -> 10.6k
 // cycles per 256 x 128 tile with the column statistics on DPP row sums; not kept)
-__device__ __forceinline__ f32x4_p mf16(bf16x8_p a, bf16x8_p b, f32x4_p c) {
+__device__ __forceinline__ f32x4 mf16(bf16x8 a, bf16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
@@ -87,19 +74,6 @@ __device__ __forceinline__ f32x4_p mf16(bf16x8_p a, bf16x8_p b, f32x4_p c) {
 template <int AMODE, bool SK, int PBK, bool ASPLIT = false, bool PRO = false>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(X3pGeo<PBK>::WPE)))
 gemm_x3p_kernel(const GemmArgs args) {
-#if X3P_CLOCK  // diagnostic build only (tools/r04/run27.sh): the clock this workgroup ran at, by device printf
-  const long long clk_t0 = __builtin_amdgcn_s_memtime(), clk_r0 = __builtin_amdgcn_s_memrealtime();
-  auto clk_report = [&]() {
-    const long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-    if (threadIdx.x == 0 && blockIdx.x % 16 == 0)
-      printf("x3pclk %d %lld %lld\n", (int)blockIdx.x, t1 - clk_t0, r1 - clk_r0);
-  };
-#else
-  auto clk_report = [] {};
-#endif
-#if X3P_PRIO  // A/B: the second-dispatched half of the workgroup at issue priority 1 (MI355X_MICROARCH.md, item 4)
-  if (threadIdx.x >= 256) __builtin_amdgcn_s_setprio(1);
-#endif
   STAMP_DECL;
   STAMP(capmi_x3p_stamps, kStStart, 0);
   STAMP_REAL(capmi_x3p_stamps, kStRStart);
@@ -120,9 +94,9 @@ gemm_x3p_kernel(const GemmArgs args) {
   // DMA lane geometry: row lane / CPR of an RPB-row block, slot lane % CPR
   const int drow = lane / CPR, dslot = lane % CPR;
 
-  constexpr bool M16 = PBK == 32 && X3P_M16;
+  constexpr bool M16 = PBK == 32;
   f32x16 acc[2][JN32];  // 32x32x16: wave tile 2 x JN32 blocks of 32 x 32
-  f32x4_p acc4[4][JN];  // 16x16x32: wave tile 4 x JN blocks of 16 x 16
+  f32x4 acc4[4][JN];  // 16x16x32: wave tile 4 x JN blocks of 16 x 16
 
   auto mainloop = [&](const capmi_gemm_problem& P, int m0, int n0, int k_lo, int k_hi) {
 #pragma unroll
@@ -134,27 +108,20 @@ gemm_x3p_kernel(const GemmArgs args) {
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int j = 0; j < JN; ++j) acc4[i][j] = f32x4_p{0.f, 0.f, 0.f, 0.f};
+      for (int j = 0; j < JN; ++j) acc4[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int nkt = (k_hi - k_lo) / PBK;
     if (nkt <= 0) return;
     const int M = P.M, N = P.N;
     const int cH = P.cH, cW = P.cW, cCin = P.cCin, cKW = P.cKW;
     const long long planeA = AMODE == 2 ? (long long)P.cN * cH * cW * cCin : (long long)M * P.lda;
     const long long planeB = (long long)N * P.ldb;
-#ifndef X3P_PRICE
-#define X3P_PRICE 0
-#endif
-#ifndef X3P_SKIP
-#define X3P_SKIP 0
-#endif
-    // X3P_PRICE (timing-only builds): 1 = A descriptor with zero records (no A traffic), 2 = B, 3 = both
-    const auto ra = rsrc_p(P.A, (X3P_PRICE & 1) ? 0u : (unsigned)(ASPLIT ? planeA * 4 : 3 * planeA * 2));
-    const auto rb = rsrc_p(P.B, (X3P_PRICE & 2) ? 0u : (unsigned)(3 * planeB * 2));
+    const auto ra = buf_rsrc(P.A, (unsigned)(ASPLIT ? planeA * 4 : 3 * planeA * 2));
+    const auto rb = buf_rsrc(P.B, (unsigned)(3 * planeB * 2));
     // x3d prologue: scale / shift through descriptors sized to the channel count (round 3):
     // a read past the last channel returns 0 instead of touching the next allocation
     const unsigned ss_bytes = PRO ? (unsigned)((AMODE == 2 ? cCin : P.K) * 4) : 0u;
-    const auto rsc_p = rsrc_p(PRO ? (const void*)P.in_scale : P.B, ss_bytes);
-    const auto rsh_p = rsrc_p(PRO ? (const void*)P.in_shift : P.B, ss_bytes);
+    const auto rsc_p = buf_rsrc(PRO ? (const void*)P.in_scale : P.B, ss_bytes);
+    const auto rsh_p = buf_rsrc(PRO ? (const void*)P.in_shift : P.B, ss_bytes);
     // this lane's two A rows (row blocks 2 wid, 2 wid + 1) and one B row (row block wid)
     // (arrays sized 2 >= NAB: a dependent bound in the nested lambda loses the host launch stub)
     unsigned a_base[2];  // dense: byte offset of (row, chunk) in plane 0; conv: pixel index of (n, 0, 0)
@@ -236,9 +203,6 @@ gemm_x3p_kernel(const GemmArgs args) {
 
     // DMA of k-tile kt into buffer buf: 6 A + 3 B wave-instructions per wave
     auto issue = [&](int kt, int buf) {
-#if X3P_SKIP & 1  // timing-only: no DMA
-      return;
-#endif
       const int k = k_lo + kt * PBK;
       const bool kok = k < k_hi;
       if (ASPLIT) {
@@ -260,11 +224,11 @@ gemm_x3p_kernel(const GemmArgs args) {
             ok = s_ok[i] && kok && (unsigned)ih < (unsigned)cH && (unsigned)iw < (unsigned)cW;
             off = ((s_base[i] + (unsigned)(ih * cW + iw)) * (unsigned)cCin + (unsigned)(c_ci + aq * 4)) * 4u;
           }
-          areg[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(ra, ok ? off : kOOBp, 0, 0));
+          areg[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(ra, ok ? off : kOOB, 0, 0));
           a_msk |= (unsigned)ok << i;
         }
       }
-      // plane-0 byte offset of this lane's A piece and its out-of-range bit (kOOBp: padding taps, rows past M, k past
+      // plane-0 byte offset of this lane's A piece and its out-of-range bit (kOOB: padding taps, rows past M, k past
       // the end), combined per plane below without a branch (an exec-masked offset computation split the DMA issue
       // into basic blocks of its own, out of reach of the MFMA interleave)
       unsigned aoff[2], abad[2];
@@ -273,12 +237,12 @@ gemm_x3p_kernel(const GemmArgs args) {
         if (ASPLIT) break;
         if (AMODE == 0) {
           aoff[i] = a_base[i] + (unsigned)k * 2;
-          abad[i] = a_ok[i] && kok ? 0u : kOOBp;
+          abad[i] = a_ok[i] && kok ? 0u : kOOB;
         } else {
           const int ih = a_ih0[i] + c_kh, iw = a_iw0[i] + c_kw;
           const bool ok = a_ok[i] && kok && (unsigned)ih < (unsigned)cH && (unsigned)iw < (unsigned)cW;
           aoff[i] = ((a_base[i] + (unsigned)(ih * cW + iw)) * (unsigned)cCin + (unsigned)(c_ci + c_sub * PBK + a_ch[i] * 8)) * 2u;
-          abad[i] = ok ? 0u : kOOBp;
+          abad[i] = ok ? 0u : kOOB;
         }
       }
       if (AMODE == 2 && ++c_sub == SUB) {
@@ -298,14 +262,14 @@ gemm_x3p_kernel(const GemmArgs args) {
         for (int i = 0; i < (ASPLIT ? 0 : NAB); ++i)
           __builtin_amdgcn_raw_ptr_buffer_load_lds(
               ra, (lds_ptr_t)(base + p * PBM * PROWB + (NAB * wid + i) * RPB * PROWB), 16,
-              PBK == 32 ? (aoff[i] + p * pA2) | abad[i] : (abad[i] ? kOOBp : aoff[i] + p * pA2), 0, 0, 0);
+              PBK == 32 ? (aoff[i] + p * pA2) | abad[i] : (abad[i] ? kOOB : aoff[i] + p * pA2), 0, 0, 0);
       if (bw) {
-        const unsigned boff = b_base + (unsigned)k * 2, bbad = b_ok && kok ? 0u : kOOBp;
+        const unsigned boff = b_base + (unsigned)k * 2, bbad = b_ok && kok ? 0u : kOOB;
         // (BK = 16, at its 128-register cap, keeps the select form: the branch-free one spilled it)
 #pragma unroll
         for (int p = 0; p < 3; ++p)
           __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (lds_ptr_t)(base + PA_BYTES + p * PBN * PROWB + wid * RPB * PROWB),
-                                                   16, PBK == 32 ? (boff + p * pB2) | bbad : (bbad ? kOOBp : boff + p * pB2), 0, 0, 0);
+                                                   16, PBK == 32 ? (boff + p * pB2) | bbad : (bbad ? kOOB : boff + p * pB2), 0, 0, 0);
       }
     };
     // x3d: fp32 A registers of one k-tile -> (prologue) -> three planes
@@ -315,12 +279,6 @@ gemm_x3p_kernel(const GemmArgs args) {
 #pragma unroll
       for (int i = 0; i < NSA; ++i) {
         float4 v = ar[i];
-#if X3D_NOSPLIT  // timing-only builds: no prologue / split VALU, the raw bits stored (wrong results)
-#pragma unroll
-        for (int p = 0; p < 3; ++p)
-          *reinterpret_cast<uint2*>(base + p * PBM * PROWB + s_lds[i]) = make_uint2(__float_as_uint(v.x), __float_as_uint(v.z));
-        continue;
-#endif
         if (PRO) v = make_float4(fmaxf(fmaf(v.x, sc.x, sh.x), 0.f), fmaxf(fmaf(v.y, sc.y, sh.y), 0.f),
                                  fmaxf(fmaf(v.z, sc.z, sh.z), 0.f), fmaxf(fmaf(v.w, sc.w, sh.w), 0.f));
         if (!((msk >> i) & 1u)) v = make_float4(0.f, 0.f, 0.f, 0.f);  // padding taps: zeros AFTER the BN
@@ -334,29 +292,45 @@ gemm_x3p_kernel(const GemmArgs args) {
     };
     // x3d: the registers of the k-tile loaded by the last issue()
     auto store_a = [&](int buf) { store_a_from(buf, areg, a_sc, a_sh, a_msk); };
+    // the six products of row block i of a k-tile, smallest terms first per accumulator
+    auto mm6 = [&](int i, const bf16x8 (&a)[3], const bf16x8 (&b)[JN][3]) {
+#pragma unroll
+      for (int j = 0; j < JN; ++j) {
+        acc4[i][j] = mf16(a[1], b[j][1], acc4[i][j]);
+        acc4[i][j] = mf16(a[0], b[j][2], acc4[i][j]);
+        acc4[i][j] = mf16(a[2], b[j][0], acc4[i][j]);
+      }
+#pragma unroll
+      for (int j = 0; j < JN; ++j) {
+        acc4[i][j] = mf16(a[0], b[j][1], acc4[i][j]);
+        acc4[i][j] = mf16(a[1], b[j][0], acc4[i][j]);
+        acc4[i][j] = mf16(a[0], b[j][0], acc4[i][j]);
+      }
+    };
     auto compute = [&](int buf) {
       const unsigned char* A_ = lds + buf * PBUF;
       const unsigned char* B_ = A_ + PA_BYTES;
       if constexpr (M16) {
         // 16x16x32: lane l reads row (l % 16) of each 16-row block, k-chunk l / 16 (8 k of the 32);
         // all 24 fragments of the k-tile up front, then 16 blocks x 6 products
-        bf16x8_p a[4][3], b[JN][3];
+        bf16x8 a[4][3], b[JN][3];
         const int c = lane >> 4, rl = lane & 15;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int r = wm0 + 16 * i + rl;
           const int o = r * PROWB + ((c ^ swz<PBK>(r)) << 4);
 #pragma unroll
-          for (int p = 0; p < 3; ++p) a[i][p] = *reinterpret_cast<const bf16x8_p*>(A_ + p * PBM * PROWB + o);
+          for (int p = 0; p < 3; ++p) a[i][p] = *reinterpret_cast<const bf16x8*>(A_ + p * PBM * PROWB + o);
         }
 #pragma unroll
         for (int j = 0; j < JN; ++j) {
           const int r = wn0 + 16 * j + rl;
           const int o = r * PROWB + ((c ^ swz<PBK>(r)) << 4);
 #pragma unroll
-          for (int p = 0; p < 3; ++p) b[j][p] = *reinterpret_cast<const bf16x8_p*>(B_ + p * PBN * PROWB + o);
+          for (int p = 0; p < 3; ++p) b[j][p] = *reinterpret_cast<const bf16x8*>(B_ + p * PBN * PROWB + o);
         }
-        // smallest terms first into each fp32 accumulator
+        // smallest terms first into each fp32 accumulator (mm6's products with the first three of every row block
+        // ahead of the last three: through mm6 the one-deep x3d kernels schedule differently)
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -377,7 +351,7 @@ gemm_x3p_kernel(const GemmArgs args) {
       }
       // every fragment of the k-tile is requested up front (2 x 12 ds_read_b128): the second
       // chunk's reads land while the first chunk's 24 MFMAs run
-      bf16x8_p a[PBK / 16][2][3], b[PBK / 16][JN32][3];
+      bf16x8 a[PBK / 16][2][3], b[PBK / 16][JN32][3];
 #pragma unroll
       for (int g = 0; g < PBK / 16; ++g) {
         const int c = 2 * g + lh;  // logical 16-B chunk (8 k) this lane reads
@@ -385,25 +359,15 @@ gemm_x3p_kernel(const GemmArgs args) {
         for (int i = 0; i < 2; ++i) {
           const int r = wm0 + 32 * i + lr;
           const int o = r * PROWB + ((c ^ swz<PBK>(r)) << 4);
-#if X3P_SKIP & 2  // timing-only: no LDS reads
 #pragma unroll
-          for (int p = 0; p < 3; ++p) a[g][i][p] = bf16x8_p{} + (__bf16)(float)(o + p);
-#else
-#pragma unroll
-          for (int p = 0; p < 3; ++p) a[g][i][p] = *reinterpret_cast<const bf16x8_p*>(A_ + p * PBM * PROWB + o);
-#endif
+          for (int p = 0; p < 3; ++p) a[g][i][p] = *reinterpret_cast<const bf16x8*>(A_ + p * PBM * PROWB + o);
         }
 #pragma unroll
         for (int j = 0; j < JN32; ++j) {
           const int r = wn0 + 32 * j + lr;
           const int o = r * PROWB + ((c ^ swz<PBK>(r)) << 4);
-#if X3P_SKIP & 2
 #pragma unroll
-          for (int p = 0; p < 3; ++p) b[g][j][p] = bf16x8_p{} + (__bf16)(float)(o - p);
-#else
-#pragma unroll
-          for (int p = 0; p < 3; ++p) b[g][j][p] = *reinterpret_cast<const bf16x8_p*>(B_ + p * PBN * PROWB + o);
-#endif
+          for (int p = 0; p < 3; ++p) b[g][j][p] = *reinterpret_cast<const bf16x8*>(B_ + p * PBN * PROWB + o);
         }
       }
 #pragma unroll
@@ -427,15 +391,12 @@ gemm_x3p_kernel(const GemmArgs args) {
           }
       }
     };
-#ifndef X3D_PIPE
-#define X3D_PIPE 1
-#endif
     // x3d staging helpers (round 4 pipelined loop, round 5 phase loop): B planes by LDS-DMA, A slots by register
     auto b_dma = [&](int kt, int buf) {  // B planes of tile kt (past the end: zeros) into buffer buf
       const int k = k_lo + kt * PBK;
       unsigned char* base = lds + buf * PBUF;
       if (bw) {
-        const unsigned boff = b_base + (unsigned)k * 2, bbad = b_ok && k < k_hi ? 0u : kOOBp;
+        const unsigned boff = b_base + (unsigned)k * 2, bbad = b_ok && k < k_hi ? 0u : kOOB;
 #pragma unroll
         for (int p = 0; p < 3; ++p)
           __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (lds_ptr_t)(base + PA_BYTES + p * PBN * PROWB + wid * RPB * PROWB),
@@ -455,14 +416,14 @@ gemm_x3p_kernel(const GemmArgs args) {
         ok = s_ok[i] && kok && (unsigned)ih < (unsigned)cH && (unsigned)iw < (unsigned)cW;
         off = ((s_base[i] + (unsigned)(ih * cW + iw)) * (unsigned)cCin + (unsigned)(c_ci + aq * 4)) * 4u;
       }
-      areg[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(ra, off | (ok ? 0u : kOOBp), 0, 0));
+      areg[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(ra, off | (ok ? 0u : kOOB), 0, 0));
       a_msk = (a_msk & ~(1u << i)) | ((unsigned)ok << i);
     };
     auto a_next = [&](int kt) {  // after tile kt's four slots: its BN scale / shift, then the walk advances
       const int k = k_lo + kt * PBK;
       if (PRO) {  // always two loads (the step's vmcnt count relies on it); past the last k-tile the walk is
                   // past Cin: an out-of-range offset, zeros
-        const unsigned ch = k < k_hi ? (unsigned)((AMODE == 2 ? c_ci : k) + aq * 4) * 4u : kOOBp;
+        const unsigned ch = k < k_hi ? (unsigned)((AMODE == 2 ? c_ci : k) + aq * 4) * 4u : kOOB;
         a_sc = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsc_p, ch, 0, 0));
         a_sh = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsh_p, ch, 0, 0));
       }
@@ -477,12 +438,6 @@ gemm_x3p_kernel(const GemmArgs args) {
     auto a_split = [&](int buf, int i) {  // slot i -> (prologue) -> three planes of buffer buf
       unsigned char* base = lds + buf * PBUF;
       float4 v = areg[i];
-#if X3D_NOSPLIT  // timing-only builds (above)
-#pragma unroll
-      for (int p = 0; p < 3; ++p)
-        *reinterpret_cast<uint2*>(base + p * PBM * PROWB + s_lds[i]) = make_uint2(__float_as_uint(v.x), __float_as_uint(v.z));
-      return;
-#endif
       if (PRO) v = make_float4(fmaxf(fmaf(v.x, a_sc.x, a_sh.x), 0.f), fmaxf(fmaf(v.y, a_sc.y, a_sh.y), 0.f),
                                fmaxf(fmaf(v.z, a_sc.z, a_sh.z), 0.f), fmaxf(fmaf(v.w, a_sc.w, a_sh.w), 0.f));
       const bool keep = (a_msk >> i) & 1u;  // padding taps / rows past M: zeros AFTER the BN
@@ -497,27 +452,7 @@ gemm_x3p_kernel(const GemmArgs args) {
       for (int p = 0; p < 3; ++p)
         *reinterpret_cast<uint2*>(base + p * PBM * PROWB + s_lds[i]) = make_uint2(lo[p], hi[p]);
     };
-// X3P_PHASE (round 5, default 2): x3p's k-loop places its one barrier after this many row blocks' MFMAs and
-// issues the next-but-one tile's DMA behind it (see the x3p branch of mainloop); 0 = the round-4 loop
-#ifndef X3P_PHASE
-#define X3P_PHASE 2
-#endif
-    // the six products of row block i of a k-tile, smallest terms first per accumulator
-    auto mm6 = [&](int i, const bf16x8_p (&a)[3], const bf16x8_p (&b)[JN][3]) {
-#pragma unroll
-      for (int j = 0; j < JN; ++j) {
-        acc4[i][j] = mf16(a[1], b[j][1], acc4[i][j]);
-        acc4[i][j] = mf16(a[0], b[j][2], acc4[i][j]);
-        acc4[i][j] = mf16(a[2], b[j][0], acc4[i][j]);
-      }
-#pragma unroll
-      for (int j = 0; j < JN; ++j) {
-        acc4[i][j] = mf16(a[0], b[j][1], acc4[i][j]);
-        acc4[i][j] = mf16(a[1], b[j][0], acc4[i][j]);
-        acc4[i][j] = mf16(a[0], b[j][0], acc4[i][j]);
-      }
-    };
-    if (ASPLIT && M16 && X3D_PIPE && args.x3d_pipe) {
+    if (ASPLIT && M16 && args.x3d_pipe) {
       // x3d, round 4: A two k-tiles deep in ONE register set. During tile kt's MFMAs each of the thread's four
       // float4 slots is split into the other buffer for tile kt + 1 and at once reloaded with tile kt + 2's
       // (its BN scale / shift and the conv walk follow after the fourth slot): the A load has a whole k-tile to
@@ -525,13 +460,13 @@ gemm_x3p_kernel(const GemmArgs args) {
       // k-tiles with the load latency in front of them (the one-deep form: issue, MFMAs, wait, split, barrier)
       const int c16 = lane >> 4, rl16 = lane & 15;
       auto frag = [&](const unsigned char* plane, int r) {  // 16x16x32 fragment of row r, chunk c16
-        return *reinterpret_cast<const bf16x8_p*>(plane + r * PROWB + ((c16 ^ swz<PBK>(r)) << 4));
+        return *reinterpret_cast<const bf16x8*>(plane + r * PROWB + ((c16 ^ swz<PBK>(r)) << 4));
       };
       auto step = [&](int kt, int buf) {
         b_dma(kt + 1, buf ^ 1);  // buffer buf ^ 1 was last read by the previous step (barrier since)
         const unsigned char* A_ = lds + buf * PBUF;
         const unsigned char* B_ = A_ + PA_BYTES;
-        bf16x8_p b[JN][3], a[3];
+        bf16x8 b[JN][3], a[3];
 #pragma unroll
         for (int j = 0; j < JN; ++j)
 #pragma unroll
@@ -540,7 +475,7 @@ gemm_x3p_kernel(const GemmArgs args) {
         for (int p = 0; p < 3; ++p) a[p] = frag(A_ + p * PBM * PROWB, wm0 + rl16);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          bf16x8_p an[3];
+          bf16x8 an[3];
           if (i + 1 < 4) {
 #pragma unroll
             for (int p = 0; p < 3; ++p) an[p] = frag(A_ + p * PBM * PROWB, wm0 + 16 * (i + 1) + rl16);
@@ -549,19 +484,7 @@ gemm_x3p_kernel(const GemmArgs args) {
           a_split(buf ^ 1, i);
           a_load(kt + 2, i);
           if (i == 3) a_next(kt + 2);
-          // per accumulator the six products smallest terms first (the one-deep form's order)
-#pragma unroll
-          for (int j = 0; j < JN; ++j) {
-            acc4[i][j] = mf16(a[1], b[j][1], acc4[i][j]);
-            acc4[i][j] = mf16(a[0], b[j][2], acc4[i][j]);
-            acc4[i][j] = mf16(a[2], b[j][0], acc4[i][j]);
-          }
-#pragma unroll
-          for (int j = 0; j < JN; ++j) {
-            acc4[i][j] = mf16(a[0], b[j][1], acc4[i][j]);
-            acc4[i][j] = mf16(a[1], b[j][0], acc4[i][j]);
-            acc4[i][j] = mf16(a[0], b[j][0], acc4[i][j]);
-          }
+          mm6(i, a, b);
 #pragma unroll
           for (int r = 0; r < 24; ++r) {  // one MFMA, then up to two VALU (the slot's split)
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -598,7 +521,7 @@ gemm_x3p_kernel(const GemmArgs args) {
       __syncthreads();  // (the next tile's prologue rewrites buffer 0, which the last step may have read)
       return;
     }
-    if (!ASPLIT && M16 && X3P_PHASE) {
+    if (!ASPLIT && M16) {
       // x3p, round 5: the DMA of tile kt + 2 is issued right after the barrier that ends the reads of tile kt
       // (into the buffer those reads used), interleaved with the second half of tile kt's MFMAs, so each tile's
       // DMA has a whole k-tile to land; the one-barrier loop below issued it ahead of the reads and waited for
@@ -611,33 +534,26 @@ gemm_x3p_kernel(const GemmArgs args) {
       for (int kt = 0; kt < nkt; ++kt) {
         const unsigned char* A_ = lds + (kt & 1) * PBUF;
         const unsigned char* B_ = A_ + PA_BYTES;
-        bf16x8_p a[4][3], b[JN][3];
+        bf16x8 a[4][3], b[JN][3];
 #pragma unroll
         for (int j = 0; j < JN; ++j) {
           const int r = wn0 + 16 * j + rl;
           const int o = r * PROWB + ((c ^ swz<PBK>(r)) << 4);
 #pragma unroll
-#if X3P_SKIP & 2  // timing-only: no LDS reads
-          for (int p = 0; p < 3; ++p) b[j][p] = bf16x8_p{} + (__bf16)(float)(o - p);
-#else
-          for (int p = 0; p < 3; ++p) b[j][p] = *reinterpret_cast<const bf16x8_p*>(B_ + p * PBN * PROWB + o);
-#endif
+          for (int p = 0; p < 3; ++p) b[j][p] = *reinterpret_cast<const bf16x8*>(B_ + p * PBN * PROWB + o);
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int r = wm0 + 16 * i + rl;
           const int o = r * PROWB + ((c ^ swz<PBK>(r)) << 4);
 #pragma unroll
-#if X3P_SKIP & 2  // timing-only: no LDS reads
-          for (int p = 0; p < 3; ++p) a[i][p] = bf16x8_p{} + (__bf16)(float)(o + p);
-#else
-          for (int p = 0; p < 3; ++p) a[i][p] = *reinterpret_cast<const bf16x8_p*>(A_ + p * PBM * PROWB + o);
-#endif
+          for (int p = 0; p < 3; ++p) a[i][p] = *reinterpret_cast<const bf16x8*>(A_ + p * PBM * PROWB + o);
         }
-        // X3P_PHASE = row blocks multiplied before the barrier (1-3)
+        // two of the four row blocks are multiplied before the barrier (round 5; one or three moved the time by a
+        // few percent only)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          if (i == X3P_PHASE) {
+          if (i == 2) {
             __builtin_amdgcn_sched_barrier(0);
             // tile kt + 1 landed (this wave's DMA), this wave's reads of tile kt done; the barrier makes both hold
             // for every wave: buffer kt & 1 is free for tile kt + 2, buffer (kt + 1) & 1 readable
@@ -649,7 +565,7 @@ gemm_x3p_kernel(const GemmArgs args) {
         }
 #pragma unroll
         for (int r = 0; r < 9; ++r) {  // the DMA pieces spread over the MFMAs after the barrier
-          __builtin_amdgcn_sched_group_barrier(0x008, 2 * (4 - X3P_PHASE), 0);
+          __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
           __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -664,13 +580,9 @@ gemm_x3p_kernel(const GemmArgs args) {
     for (int kt = 0; kt < nkt; ++kt) {
       issue(kt + 1, (kt + 1) & 1);  // past the end: OOB loads (zeros) into the idle buffer
       compute(kt & 1);
-#if X3P_SKIP & 4  // timing-only: no barrier inside the k-loop
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       store_a((kt + 1) & 1);  // x3d: buffer (kt + 1) & 1 was last read by compute(kt - 1)
       __syncthreads();
-#endif
     }
   };
 
@@ -689,14 +601,14 @@ gemm_x3p_kernel(const GemmArgs args) {
       if (args.plain_epi) {
         // store-only form (host: plain_epilogue): 16 row offsets per lane computed once, the 64 stores
         // take the column block as an immediate offset; rows past M are dropped by the descriptor
-        const auto rc = rsrc_p(C, (unsigned)((long long)M * ldc * 4));
+        const auto rc = buf_rsrc(C, (unsigned)((long long)M * ldc * 4));
         unsigned roff[4][4];
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int row = m0 + wm0 + 16 * i + 4 * rq + r;
-            roff[i][r] = row < M ? (unsigned)row * (unsigned)ldc * 4u : kOOBp;
+            roff[i][r] = row < M ? (unsigned)row * (unsigned)ldc * 4u : kOOB;
           }
         const unsigned cb = (unsigned)(n0 + wn0 + cl) * 4u;
         // + beta C (plain_epi 2): each column block's 16 C values loaded before its first store. Interleaved, each
@@ -846,7 +758,6 @@ gemm_x3p_kernel(const GemmArgs args) {
     STAMP(capmi_x3p_stamps, kStMain, 0);
     epilogue(P, tm, tn);
     STAMP(capmi_x3p_stamps, kStEpi, 0);
-    clk_report();
     STAMP(capmi_x3p_stamps, kStEnd, 0);
     STAMP_REAL(capmi_x3p_stamps, kStREnd);
     return;
@@ -901,8 +812,8 @@ gemm_x3p_kernel(const GemmArgs args) {
         for (int i = 0; i < 4; ++i)
 #pragma unroll
           for (int j = 0; j < JN; ++j)
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_p, acc4[i][j]), rs,
-                                                   ((i * JN + j) * PNT + tid) * 16, 0, kSc1p);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc4[i][j]), rs,
+                                                   ((i * JN + j) * PNT + tid) * 16, 0, kSc1);
       } else {
 #pragma unroll
       for (int i = 0; i < 2; ++i)
@@ -910,12 +821,12 @@ gemm_x3p_kernel(const GemmArgs args) {
         for (int j = 0; j < JN32; ++j)
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            u32x4_p v;
+            u32x4 v;
             v.x = __float_as_uint(acc[i][j][4 * q + 0]);
             v.y = __float_as_uint(acc[i][j][4 * q + 1]);
             v.z = __float_as_uint(acc[i][j][4 * q + 2]);
             v.w = __float_as_uint(acc[i][j][4 * q + 3]);
-            __builtin_amdgcn_raw_buffer_store_b128(v, rs, (((i * JN32 + j) * 4 + q) * PNT + tid) * 16, 0, kSc1p);
+            __builtin_amdgcn_raw_buffer_store_b128(v, rs, (((i * JN32 + j) * 4 + q) * PNT + tid) * 16, 0, kSc1);
           }
       }
       sk_publish<kSkFenced1>(flags + blockIdx.x, tid);
@@ -933,7 +844,7 @@ gemm_x3p_kernel(const GemmArgs args) {
 #pragma unroll
             for (int j = 0; j < JN; ++j)
               acc4[i][j] += __builtin_bit_cast(
-                  f32x4_p, __builtin_amdgcn_raw_buffer_load_b128(rs, ((i * JN + j) * PNT + tid) * 16, 0, kSc1p));
+                  f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, ((i * JN + j) * PNT + tid) * 16, 0, kSc1));
         } else {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -941,8 +852,8 @@ gemm_x3p_kernel(const GemmArgs args) {
           for (int j = 0; j < JN32; ++j)
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-              const u32x4_p v =
-                  __builtin_amdgcn_raw_buffer_load_b128(rs, (((i * JN32 + j) * 4 + q) * PNT + tid) * 16, 0, kSc1p);
+              const u32x4 v =
+                  __builtin_amdgcn_raw_buffer_load_b128(rs, (((i * JN32 + j) * 4 + q) * PNT + tid) * 16, 0, kSc1);
               acc[i][j][4 * q + 0] += __uint_as_float(v.x);
               acc[i][j][4 * q + 1] += __uint_as_float(v.y);
               acc[i][j][4 * q + 2] += __uint_as_float(v.z);
@@ -956,7 +867,6 @@ gemm_x3p_kernel(const GemmArgs args) {
     epilogue(P, tm, tn);
     STAMP(capmi_x3p_stamps, kStEpi, 0);
   }
-  clk_report();
   STAMP(capmi_x3p_stamps, kStEnd, 0);
   STAMP_REAL(capmi_x3p_stamps, kStREnd);
 }

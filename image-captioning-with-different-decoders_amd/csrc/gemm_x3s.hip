@@ -16,35 +16,18 @@
 // barrier per tile. Epilogue: the store-only form (plain_epilogue: C = A.B, 32-bit row offsets per
 // tile, the column block as an immediate), per-column (sum, sum of squares) of the 64 rows reduced
 // across the wave's four row quads and written once per tile: no atomics, deterministic.
-#include "gemm_args.h"
+#include "x3_common.h"
 
 namespace {
 
 constexpr int SBM = 64;   // rows per tile (= one 64-row BN statistics slice)
 constexpr int SKD = 64;   // k (fixed)
 constexpr int SNT = 256;  // threads
-typedef __bf16 bf16x8_s __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4_s __attribute__((ext_vector_type(4)));
-typedef float f32x4_s __attribute__((ext_vector_type(4)));
-constexpr unsigned kOOBs = 0x80000000u;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_s(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
 
 // bf16 offset of 8-element chunk c (0..7) of LDS row r (128-B rows): chunk slot c ^ ((r >> 1) & 7), so
 // the 16-lane groups of the fragment reads (rows r0..r0+15, one chunk) hit 16 distinct 16-B slots mod
 // 256 B (all 64 banks), and the split stores (two whole rows per 32 lanes) are conflict-free
 __device__ __forceinline__ int soff(int r, int c) { return r * SKD + ((c ^ ((r >> 1) & 7)) << 3); }
-
-__device__ __forceinline__ bf16x4_s cvt4s(float4 v) {
-  bf16x4_s r;
-  r.x = (__bf16)v.x;
-  r.y = (__bf16)v.y;
-  r.z = (__bf16)v.z;
-  r.w = (__bf16)v.w;
-  return r;
-}
 
 // What a tile's accumulators become (x3s_body's EPI): stored with their statistics (the conv itself), the
 // statistics alone (no C at all), or the bottleneck tail -- BN + residual + ReLU -> the block output -- with the
@@ -65,10 +48,10 @@ __device__ __forceinline__ void x3s_body(const capmi_gemm_problem& P, long long 
   const int wc0 = wid * 16 * NCB;
 
   // the wave's weight fragments for the whole run: column 16 cb + rl of its block, k 32 kc + 8 c4 .. + 7
-  bf16x8_s bw[NCB][2][3];
+  bf16x8 bw[NCB][2][3];
   {
     const long long plane = (long long)N * P.ldb;
-    const auto rb = rsrc_s(P.B, (unsigned)(3 * plane * 2));
+    const auto rb = buf_rsrc(P.B, (unsigned)(3 * plane * 2));
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
@@ -76,7 +59,7 @@ __device__ __forceinline__ void x3s_body(const capmi_gemm_problem& P, long long 
 #pragma unroll
         for (int p = 0; p < 3; ++p) {
           const unsigned off = (unsigned)((p * plane + (long long)(wc0 + 16 * cb + rl) * P.ldb + 32 * kc + 8 * c4) * 2);
-          bw[cb][kc][p] = __builtin_bit_cast(bf16x8_s, __builtin_amdgcn_raw_buffer_load_b128(rb, off, 0, 0));
+          bw[cb][kc][p] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rb, off, 0, 0));
         }
   }
   // A slots: float4 s of this thread = row (tid >> 4) + 16 s, k 4 (tid & 15) .. + 3
@@ -86,7 +69,7 @@ __device__ __forceinline__ void x3s_body(const capmi_gemm_problem& P, long long 
     sc = *reinterpret_cast<const float4*>(P.in_scale + ak);
     sh = *reinterpret_cast<const float4*>(P.in_shift + ak);
   }
-  const auto ra = rsrc_s(P.A, (unsigned)((long long)M * lda * 4));
+  const auto ra = buf_rsrc(P.A, (unsigned)((long long)M * lda * 4));
   float4 areg[4];
   unsigned amsk = 0;
   auto load_a = [&](int t) {
@@ -96,7 +79,7 @@ __device__ __forceinline__ void x3s_body(const capmi_gemm_problem& P, long long 
       const int row = t * SBM + ar + 16 * s;
       const bool ok = t < tiles && row < M;
       areg[s] = __builtin_bit_cast(
-          float4, __builtin_amdgcn_raw_buffer_load_b128(ra, ok ? (unsigned)(row * lda + ak) * 4u : kOOBs, 0, 0));
+          float4, __builtin_amdgcn_raw_buffer_load_b128(ra, ok ? (unsigned)(row * lda + ak) * 4u : kOOB, 0, 0));
       amsk |= (unsigned)ok << s;
     }
   };
@@ -106,15 +89,17 @@ __device__ __forceinline__ void x3s_body(const capmi_gemm_problem& P, long long 
       float4 v = areg[s];
       if (PRO) v = relu4(fma4(v, sc, sh));
       if (!((amsk >> s) & 1u)) v = f4(0.f);  // rows past M: zeros (their outputs add nothing to the sums)
-      const bf16x4_s h0 = cvt4s(v);
+      // (x3_split4's arithmetic, kept spelled element-wise: through the helper the same values are scheduled
+      // differently)
+      const bf16x4 h0 = x3_cvt4(v);
       const float4 r1 = make_float4(v.x - (float)h0.x, v.y - (float)h0.y, v.z - (float)h0.z, v.w - (float)h0.w);
-      const bf16x4_s h1 = cvt4s(r1);
-      const bf16x4_s h2 = cvt4s(make_float4(r1.x - (float)h1.x, r1.y - (float)h1.y, r1.z - (float)h1.z,
+      const bf16x4 h1 = x3_cvt4(r1);
+      const bf16x4 h2 = x3_cvt4(make_float4(r1.x - (float)h1.x, r1.y - (float)h1.y, r1.z - (float)h1.z,
                                             r1.w - (float)h1.w));
       const int o = soff(ar + 16 * s, ak >> 3) + (ak & 4);
-      *reinterpret_cast<bf16x4_s*>(&As[buf][0][o]) = h0;
-      *reinterpret_cast<bf16x4_s*>(&As[buf][1][o]) = h1;
-      *reinterpret_cast<bf16x4_s*>(&As[buf][2][o]) = h2;
+      *reinterpret_cast<bf16x4*>(&As[buf][0][o]) = h0;
+      *reinterpret_cast<bf16x4*>(&As[buf][1][o]) = h1;
+      *reinterpret_cast<bf16x4*>(&As[buf][2][o]) = h2;
     }
   };
 
@@ -132,7 +117,7 @@ __device__ __forceinline__ void x3s_body(const capmi_gemm_problem& P, long long 
   load_a(t);
   store_a(0);
   __syncthreads();
-  const auto rc = rsrc_s(P.C, (unsigned)((long long)M * P.ldc * 4));  // (statistics pass: never accessed)
+  const auto rc = buf_rsrc(P.C, (unsigned)((long long)M * P.ldc * 4));  // (statistics pass: never accessed)
   const unsigned cbo = (unsigned)(wc0 + rl) * 4u;
   float* __restrict__ stats = P.stats;
   // tail: the `other` values of ONE column block (16 rows of this lane's column) and that column's BN
@@ -143,7 +128,7 @@ __device__ __forceinline__ void x3s_body(const capmi_gemm_problem& P, long long 
   // M ld 4 bytes, the size of both descriptors, so they are neither loaded nor stored (the host bounds
   // (M + 63) ld 4 below 2^32: no wrap)
   float ov[16], bnp[4];
-  const auto ro = rsrc_s(E.other, (unsigned)((long long)M * E.ld_other * 4));
+  const auto ro = buf_rsrc(E.other, (unsigned)((long long)M * E.ld_other * 4));
   const unsigned ldo4 = (unsigned)E.ld_other * 4u, ldc4 = (unsigned)P.ldc * 4u;
   unsigned obase = 0, cbase = 0;
   auto load_o = [&](int cb) {
@@ -171,28 +156,21 @@ __device__ __forceinline__ void x3s_body(const capmi_gemm_problem& P, long long 
       load_o(0);  // in flight across the tile's MFMAs
     }
     __builtin_amdgcn_sched_barrier(0);
-    f32x4_s acc[4][NCB];
+    f32x4 acc[4][NCB];
 #pragma unroll
     for (int rb = 0; rb < 4; ++rb) {
-      bf16x8_s a[2][3];
+      bf16x8 a[2][3];
 #pragma unroll
       for (int kc = 0; kc < 2; ++kc)
 #pragma unroll
         for (int p = 0; p < 3; ++p)
-          a[kc][p] = *reinterpret_cast<const bf16x8_s*>(&As[buf][p][soff(16 * rb + rl, 4 * kc + c4)]);
+          a[kc][p] = *reinterpret_cast<const bf16x8*>(&As[buf][p][soff(16 * rb + rl, 4 * kc + c4)]);
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb) {
-        f32x4_s c = f32x4_s{0.f, 0.f, 0.f, 0.f};
+        f32x4 c = f32x4{0.f, 0.f, 0.f, 0.f};
         // smallest terms first into the fp32 accumulator, k-block by k-block
 #pragma unroll
-        for (int kc = 0; kc < 2; ++kc) {
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[kc][1], bw[cb][kc][1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[kc][0], bw[cb][kc][2], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[kc][2], bw[cb][kc][0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[kc][0], bw[cb][kc][1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[kc][1], bw[cb][kc][0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[kc][0], bw[cb][kc][0], c, 0, 0, 0);
-        }
+        for (int kc = 0; kc < 2; ++kc) c = x3_mfma6(a[kc], bw[cb][kc], c);
         acc[rb][cb] = c;
       }
     }
@@ -228,7 +206,7 @@ __device__ __forceinline__ void x3s_body(const capmi_gemm_problem& P, long long 
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int row = t * SBM + 16 * rb + 4 * c4 + r;
-            roff[rb][r] = row < M ? (unsigned)row * (unsigned)P.ldc * 4u : kOOBs;
+            roff[rb][r] = row < M ? (unsigned)row * (unsigned)P.ldc * 4u : kOOB;
           }
       }
 #pragma unroll

@@ -20,7 +20,7 @@
 // gemm_w16_kernel (round 6, CAPMI_GEMM_X3W | CAPMI_GEMM_BF16): the same kernel with one term per operand -- each
 // fp32 value rounded to bf16 (RNE, the CAPMI_GEMM_BF16 operand contract) and one product per block -- for the
 // bf16 configuration's decoder weight gradients (capmi/decoder_core.py).
-#include "gemm_args.h"
+#include "x3_common.h"
 
 namespace {
 
@@ -31,15 +31,8 @@ constexpr int WA_PLANE = WBK * WA_ROWB;     // 16 KiB
 constexpr int WB_PLANE = WBK * WB_ROWB;     // 8 KiB
 constexpr int WA_BYTES = 3 * WA_PLANE;      // 48 KiB
 constexpr int WBUF = WA_BYTES + 3 * WB_PLANE;  // 72 KiB per buffer
-constexpr unsigned kOOBw = 0x80000000u;
-typedef float f32x4_w __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8_w __attribute__((ext_vector_type(8)));
 typedef short s16x4_w __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4_w* lds_s16x4_w;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_w(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
 
 // 16-B chunk c of k-row r is stored in slot c ^ wsw(r). A transposed read's 32-lane half takes k-rows
 // {8h .. 8h+3, 8h+8 .. 8h+11} (or those + 4) x the same 32 bytes of columns; rows 256 / 512 B apart share
@@ -62,23 +55,23 @@ __device__ __forceinline__ void wgrad_body(const GemmArgs& args) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm0 = (wid >> 1) * 64, wn0 = (wid & 1) * 64;
-  f32x4_w acc4[4][4];
+  f32x4 acc4[4][4];
 
   auto mainloop = [&](const capmi_gemm_problem& P, int m0, int n0, int k_lo, int k_hi) {
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) acc4[i][j] = f32x4_w{0.f, 0.f, 0.f, 0.f};
+      for (int j = 0; j < 4; ++j) acc4[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int nkt = (k_hi - k_lo + WBK - 1) / WBK;
     if (nkt <= 0) return;
     const int M = P.M, N = P.N;
     const long long planeB = BMODE == 2 ? (long long)P.cN * P.cH * P.cW * P.cCin : (long long)P.K * P.ldb;
-    const auto ra = rsrc_w(P.A, (unsigned)((long long)P.K * P.lda * 4));
-    const auto rb = rsrc_w(P.B, (unsigned)(planeB * 4));
+    const auto ra = buf_rsrc(P.A, (unsigned)((long long)P.K * P.lda * 4));
+    const auto rb = buf_rsrc(P.B, (unsigned)(planeB * 4));
     // prologue scale / shift through descriptors sized to the channel count (a read past it returns 0)
     const unsigned ss_bytes = P.in_scale ? (unsigned)((BMODE == 2 ? P.cCin : N) * 4) : 0u;
-    const auto rsc = rsrc_w(P.in_scale ? (const void*)P.in_scale : P.A, ss_bytes);
-    const auto rsh = rsrc_w(P.in_shift ? (const void*)P.in_shift : P.A, ss_bytes);
+    const auto rsc = buf_rsrc(P.in_scale ? (const void*)P.in_scale : P.A, ss_bytes);
+    const auto rsh = buf_rsrc(P.in_shift ? (const void*)P.in_shift : P.A, ss_bytes);
     // A = dY fp32 [k][lda]: a k-tile is 32 rows x 256 columns = 2048 float4, 4 per thread: float4 f =
     // tid + 512 i is row tid / 64 + 8 i, columns m0 + 4 (tid % 64) (one wave writes one whole LDS row)
     const int a_c4 = tid & 63, a_r0 = tid >> 6;
@@ -129,12 +122,12 @@ __device__ __forceinline__ void wgrad_body(const GemmArgs& args) {
         const int row = k + a_r0 + 8 * pc;
         const bool ok = a_mok && row < k_hi;
         ra4[pc] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                 ra, ok ? (unsigned)(((long long)row * P.lda + m0 + 4 * a_c4) * 4) : kOOBw, 0, 0));
+                                                 ra, ok ? (unsigned)(((long long)row * P.lda + m0 + 4 * a_c4) * 4) : kOOB, 0, 0));
         return;
       }
       const int i = pc - 4;
       const int pix = k + b_r0 + 16 * i;
-      unsigned off = kOOBw;
+      unsigned off = kOOB;
       if (BMODE == 2) {
         const int ih = poh[i] * P.cStride - P.cPad + b_kh, iw = pow_[i] * P.cStride - P.cPad + b_kw;
         if (b_nok && pix < k_hi && (unsigned)ih < (unsigned)P.cH && (unsigned)iw < (unsigned)P.cW)
@@ -156,7 +149,7 @@ __device__ __forceinline__ void wgrad_body(const GemmArgs& args) {
         off = (unsigned)(((long long)pix * P.ldb + b_n) * 4);
       }
       rb4[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rb, off, 0, 0));
-      bmask = (bmask & ~(1u << i)) | ((unsigned)(off != kOOBw) << i);
+      bmask = (bmask & ~(1u << i)) | ((unsigned)(off != kOOB) << i);
     };
     // registers -> (B: BN-apply + ReLU, padding taps zero AFTER it) -> three swizzled bf16 planes
     auto store_piece = [&](int buf, int pc) {
@@ -203,20 +196,20 @@ __device__ __forceinline__ void wgrad_body(const GemmArgs& args) {
       auto frag = [&](const unsigned char* plane, int rowb, int col) {
         const s16x4_w lo = tr_read(plane, rowb, g8 + q, col);
         const s16x4_w hi = tr_read(plane, rowb, g8 + 4 + q, col);
-        return __builtin_bit_cast(bf16x8_w, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+        return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
       };
-      bf16x8_w b[4][TERMS];
+      bf16x8 b[4][TERMS];
 #pragma unroll
       for (int j = 0; j < 4; ++j)
 #pragma unroll
         for (int p = 0; p < TERMS; ++p) b[j][p] = frag(B_ + p * WB_PLANE, WB_ROWB, wn0 + 16 * j + c4);
       // A fragments one 16-row block at a time (12 VGPRs live instead of 48)
-      bf16x8_w a[TERMS];
+      bf16x8 a[TERMS];
 #pragma unroll
       for (int p = 0; p < TERMS; ++p) a[p] = frag(A_ + p * WA_PLANE, WA_ROWB, wm0 + c4);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        bf16x8_w an[TERMS];
+        bf16x8 an[TERMS];
         if (i + 1 < 4) {
 #pragma unroll
           for (int p = 0; p < TERMS; ++p) an[p] = frag(A_ + p * WA_PLANE, WA_ROWB, wm0 + 16 * (i + 1) + c4);
@@ -282,14 +275,14 @@ __device__ __forceinline__ void wgrad_body(const GemmArgs& args) {
     const long long ldc = P.ldc;
     const int cl = lane & 15, rq = lane >> 4;
     if (args.plain_epi) {  // store-only form (host: plain_epilogue): 16 row offsets per lane once
-      const auto rc = rsrc_w(C, (unsigned)((long long)M * ldc * 4));
+      const auto rc = buf_rsrc(C, (unsigned)((long long)M * ldc * 4));
       unsigned roff[4][4];
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int row = m0 + wm0 + 16 * i + 4 * rq + r;
-          roff[i][r] = row < M ? (unsigned)row * (unsigned)ldc * 4u : kOOBw;
+          roff[i][r] = row < M ? (unsigned)row * (unsigned)ldc * 4u : kOOB;
         }
       const unsigned cb = (unsigned)(n0 + wn0 + cl) * 4u;
       float cold[4][4][4];  // + beta C: all loads before the first store (they may alias: no interleaving)
@@ -355,7 +348,7 @@ __device__ __forceinline__ void wgrad_body(const GemmArgs& args) {
   }
   // k-split: the raw partial into slab z of the workspace ([S][M][ldp], ldp = tiles_n * WBN)
   const int ldp = tiles_n * WBN;
-  const auto rc = rsrc_w(args.sk_part + (long long)z * P.M * ldp, (unsigned)((long long)P.M * ldp * 4));
+  const auto rc = buf_rsrc(args.sk_part + (long long)z * P.M * ldp, (unsigned)((long long)P.M * ldp * 4));
   const int cl = lane & 15, rq = lane >> 4;
   const int m0 = tm * WBM, n0 = tn * WBN;
   const unsigned cb = (unsigned)(n0 + wn0 + cl) * 4u;
@@ -364,7 +357,7 @@ __device__ __forceinline__ void wgrad_body(const GemmArgs& args) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int row = m0 + wm0 + 16 * i + 4 * rq + r;
-      const unsigned ro = row < P.M ? (unsigned)row * (unsigned)ldp * 4u : kOOBw;
+      const unsigned ro = row < P.M ? (unsigned)row * (unsigned)ldp * 4u : kOOB;
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc4[i][j][r]), rc, ro + cb + 64u * j, 0, 0);
