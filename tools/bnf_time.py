@@ -6,7 +6,8 @@ import torch
 sys.path.insert(0, "image-captioning-with-different-decoders_amd")
 from capmi import kernels as K  # noqa: E402
 
-SHAPES = [(196, 256), (196, 1024), (49, 512), (49, 2048), (784, 128), (784, 512), (3136, 64), (3136, 256)]
+SHAPES = [(196, 256), (196, 1024), (49, 512), (49, 2048), (784, 128), (784, 256), (784, 512), (3136, 64), (3136, 256),
+          (12544, 64)]
 
 
 def main():
