@@ -156,6 +156,13 @@ _SIGS = {
                             c_int, c_vp, c_vp, c_vp],
     "capmi_eval_rows_at": [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
     "capmi_eval_captions_ce": [c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp],
+    "capmi_lstm_step_fwd_train": [c_vp, c_ll, c_vp, c_ll, c_int, c_vp, c_ll, c_vp, c_ll, c_vp, c_vp, c_vp, c_vp,
+                                  c_int, c_int, c_vp, c_vp, c_vp, c_vp],
+    "capmi_lstm_step_bwd": [c_vp, c_ll, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp],
+    "capmi_count_targets": [c_vp, c_int, c_int, c_int, c_int, c_ll, c_vp, c_vp, c_vp],
+    "capmi_ce_ignore_fwd_bwd": [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_ll, c_vp, c_vp, c_vp, c_int,
+                                c_vp],
+    "capmi_loss_finalize_dev": [c_vp, c_int, c_vp, c_vp, c_vp],
     "capmi_adam_clamp": [c_vp, c_vp, c_vp, c_vp, c_ll, c_double, c_double, c_double, c_double, c_double,
                          c_double, c_double, c_vp, c_vp],
     "capmi_adam_clamp_f64": [c_vp, c_vp, c_vp, c_vp, c_ll, c_double, c_double, c_double, c_double,

@@ -751,6 +751,64 @@ def lstm_step_fwd(R, M, H, h_out, c_out, *, pre=None, ld_pre=0, x=None, ld_x=0, 
          ptr(h_out), ptr(c_out), stream())
 
 
+# --------------------------------------------------------------------------------------
+# baseline (LSTM) captioner in training (csrc/baseline_step.hip, csrc/baseline_train.hip)
+# --------------------------------------------------------------------------------------
+def lstm_step_fwd_train(R, M, H, h_out, c_out, act_out, *, pre=None, ld_pre=0, x=None, ld_x=0, h_prev=None, ld_h=0,
+                        c_prev=None, ld_c=0, w_ih=None, w_hh=None, b_ih=None, b_hh=None):
+    """lstm_step_fwd that also writes act_out (R, 4H) = (sig i | sig f | tanh g | sig o) for the backward."""
+    _cuda(pre, x, h_prev, c_prev, w_ih, w_hh, b_ih, b_hh, h_out, c_out, act_out)
+    assert h_out.is_contiguous() and c_out.is_contiguous() and min(h_out.numel(), c_out.numel()) >= R * H
+    assert act_out is None or (act_out.is_contiguous() and act_out.numel() >= R * 4 * H)
+    assert (w_ih is None or (w_ih.is_contiguous() and w_ih.numel() == 4 * H * M))
+    assert (w_hh is None or (w_hh.is_contiguous() and w_hh.numel() == 4 * H * H))
+    assert all(b is None or b.numel() == 4 * H for b in (b_ih, b_hh))
+    call("capmi_lstm_step_fwd_train", ptr(pre), int(ld_pre or 4 * H), ptr(x), int(ld_x or M), int(M), ptr(h_prev),
+         int(ld_h or H), ptr(c_prev), int(ld_c or H), ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh), int(R), int(H),
+         ptr(h_out), ptr(c_out), ptr(act_out), stream())
+
+
+def lstm_step_bwd(R, H, act, c_cur, dgates, dc_out, *, dh_lin=None, ld_dh=0, dg_next=None, w_hh=None, dc_in=None,
+                  c_prev=None):
+    """One BPTT step in one launch: dh = dh_lin + dg_next . W_hh (each optional), then the cell backward;
+    writes dgates (R, 4H) and dc_out (R, H). dg_next None (the last step): no GEMM."""
+    _cuda(dh_lin, dg_next, w_hh, dc_in, act, c_prev, c_cur, dgates, dc_out)
+    for x, n in ((act, 4 * H), (dgates, 4 * H), (dg_next, 4 * H), (c_cur, H), (c_prev, H), (dc_in, H), (dc_out, H)):
+        assert x is None or (x.is_contiguous() and x.numel() >= R * n)
+    assert w_hh is None or (w_hh.is_contiguous() and w_hh.numel() == 4 * H * H)
+    call("capmi_lstm_step_bwd", ptr(dh_lin), int(ld_dh or H), ptr(dg_next), ptr(w_hh), ptr(dc_in), ptr(act),
+         ptr(c_prev), ptr(c_cur), int(R), int(H), ptr(dgates), ptr(dc_out), stream())
+
+
+def count_targets(caps, B, T, L, tgt_off, ignore_index, count, inv_count):
+    """count[0] (int32, optional) = live targets caps[b][t + tgt_off] != ignore_index, inv_count[0] = 1 / count."""
+    _cuda(caps, dtype=torch.int64)
+    _cuda(count, dtype=torch.int32)
+    _cuda(inv_count)
+    assert caps.is_contiguous() and caps.numel() >= B * L
+    call("capmi_count_targets", ptr(caps), B, T, L, int(tgt_off), int(ignore_index), ptr(count), ptr(inv_count),
+         stream())
+
+
+def ce_ignore_fwd_bwd(logits, caps, B, T, L, V, tgt_off, ignore_index, inv_count, loss_rows, dlogits=None,
+                      dl_time_major=False):
+    """CrossEntropyLoss(ignore_index) rows and gradient; the divisor is read from the device (count_targets)."""
+    _cuda(logits, inv_count, loss_rows, dlogits)
+    _cuda(caps, dtype=torch.int64)
+    assert logits.is_contiguous() and logits.numel() >= B * T * V and loss_rows.numel() >= B * T
+    assert caps.is_contiguous() and caps.numel() >= B * L
+    assert dlogits is None or (dlogits.is_contiguous() and dlogits.numel() >= B * T * V)
+    call("capmi_ce_ignore_fwd_bwd", ptr(logits), ptr(caps), B, T, L, V, int(tgt_off), int(ignore_index),
+         ptr(inv_count), ptr(loss_rows), ptr(dlogits), int(dl_time_major), stream())
+
+
+def loss_finalize_dev(loss_rows, n, inv_count, out):
+    """out[0] = sum(loss_rows[:n]) * inv_count[0] (one workgroup, fixed order)."""
+    _cuda(loss_rows, inv_count, out)
+    assert loss_rows.numel() >= n
+    call("capmi_loss_finalize_dev", ptr(loss_rows), n, ptr(inv_count), ptr(out), stream())
+
+
 def ce_fwd_bwd(logits, caps, B, T, L, V, bt_dev, nrows, loss_rows, lse=None, dlogits=None,
                dl_time_major=False, gscale=None):
     _cuda(logits, loss_rows, lse, dlogits, gscale)

@@ -20,6 +20,10 @@
 // Arithmetic: the fp32-accurate x3 split on v_mfma_f32_16x16x32_bf16 (six products per block, smallest
 // first, fp32 accumulation), as the other decoder GEMMs (gemm_x3.hip, decoder_step.hip). The split happens
 // once per value, on the way into LDS (three bf16 planes); the cell's activations are taken in fp64.
+//
+// Training (below the inference kernel's body): the TRAIN arm of the same kernel also stores the activations
+// (capmi_lstm_step_fwd_train), and lstm_step_bwd_kernel is one backward-through-time step with the same
+// ownership (capmi_lstm_step_bwd).
 #include "gemm_args.h"
 
 namespace {
@@ -46,10 +50,15 @@ struct LsArgs {
   int M, H, R;
   int kt_x, kt;  // k-tiles of the x segment, and of both
   float *h_out, *c_out;
+  float* act_out;  // TRAIN arm only: [R][4H] = (sig i | sig f | tanh g | sig o), what a backward step reads
 };
 
 __device__ __forceinline__ double sig_l(double v) { return 1.0 / (1.0 + exp(-v)); }
 
+// TRAIN: the training forward step. The same tile, k-group order and fp64 cell, so h_out / c_out are the
+// inference arm's bits; the four fp64 activations are also stored, rounded to fp32, in capmi_lstm_cell_fwd's
+// act_out layout.
+template <bool TRAIN>
 __global__ void __launch_bounds__(256 * LS_KG) lstm_step_kernel(const LsArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned lds[LS_KG * LS_GBUF];
   const int tid = threadIdx.x, grp = tid >> 8, t = tid & 255, lane = t & 63, w = t >> 6;
@@ -191,14 +200,173 @@ __global__ void __launch_bounds__(256 * LS_KG) lstm_step_kernel(const LsArgs a) 
   const long long o = (long long)row * H + u;
   a.c_out[o] = (float)c;
   a.h_out[o] = (float)(og * tanh(c));
+  if constexpr (TRAIN) {
+    float* act = a.act_out + (long long)row * 4 * H + u;
+    act[0] = (float)ig;
+    act[H] = (float)fg;
+    act[2 * H] = (float)cg;
+    act[3 * H] = (float)og;
+  }
 }
 
-}  // namespace
+// --------------------------------------------------------------------------------------------------------
+// One backward-through-time step in one launch: the recurrent GEMM first, the cell in its epilogue.
+//
+//   dh[r][u] = dh_lin[r][u] + sum_{k < 4H} dg_next[r][k] W_hh[k][u]        (each term optional)
+//   then lstm_cell_bwd_kernel's formulas (decoder.hip) on act, c_prev, c_cur, dc_in -> dgates, dc_out
+//
+// Ownership as the forward: a workgroup owns 64 rows x 16 units (H = 512: 32 workgroups) and the whole
+// k = 4H range, dealt to the same four k-groups whose sums meet in LDS and are added in group order by the
+// thread that owns the (row, unit). Nothing is handed between workgroups.
+//
+// W_hh is [4H][H] row-major: for this product its n (the unit) is contiguous, not k. It is transposed on the
+// way into LDS: a thread takes the two k-rows 2j, 2j + 1 of one unit (the 16 units of a k-row are one 64-byte
+// segment), splits the pair and stores one dword per term plane at LDS row = unit, dword j -- the layout the
+// forward's W rows have, so the fragment reads and the six products are the forward's. (A (H, 4H) copy made
+// once per training step would need a launch and 4 MB of traffic per step for nothing this staging lacks.)
+// --------------------------------------------------------------------------------------------------------
+constexpr int LB_PLANE = (LS_ROWS + LS_UNITS) * LS_LDW;  // dwords of one bf16 term: 64 A rows, 16 W^T rows
+constexpr int LB_GBUF = 3 * LB_PLANE;
+static_assert(LB_GBUF >= LS_ROWS * LS_UNITS, "the cross-group sum reuses the staging tile");
 
-extern "C" int capmi_lstm_step_fwd(const float* pre, long long ld_pre, const float* x, long long ld_x, int M,
-                                   const float* h_prev, long long ld_h, const float* c_prev, long long ld_c,
-                                   const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
-                                   int R, int H, float* h_out, float* c_out, void* stream) {
+struct LbArgs {
+  const float *dh_lin, *dg_next, *w_hh, *dc_in, *act, *c_prev, *c_cur;
+  long long ld_dh;
+  int H, R;
+  int kt;  // k-tiles of the 4H range; 0 without dg_next (the last step: no GEMM)
+  float *dgates, *dc_out;
+};
+
+__global__ void __launch_bounds__(256 * LS_KG) lstm_step_bwd_kernel(const LbArgs a) {
+  __shared__ __attribute__((aligned(16))) unsigned lds[LS_KG * LB_GBUF];
+  const int tid = threadIdx.x, grp = tid >> 8, t = tid & 255, lane = t & 63, w = t >> 6;
+  const int tn = blockIdx.x, m0 = blockIdx.y * LS_ROWS;
+  const int R = a.R, H = a.H, K = 4 * H;
+  const int g0 = a.kt * grp / LS_KG, ng = a.kt * (grp + 1) / LS_KG - g0;
+  const int ngmax = (a.kt + LS_KG - 1) / LS_KG;
+  unsigned* Gs = lds + grp * LB_GBUF;
+
+  // staging: A (dg_next) rows ar, ar + 32, 16 B at k offset ak; W_hh rows k = 2 bj, 2 bj + 1 of unit bu
+  const int ar = t >> 3, ak = (t & 7) * 4;
+  const int bj = t >> 4, bu = t & 15;
+  const int wunit = tn * LS_UNITS + bu;
+  const bool wok = wunit < H;
+
+  f32x4_l acc = f32x4_l{0.f, 0.f, 0.f, 0.f};
+  struct Stage {
+    float4 ra[2];
+    float w0, w1;
+  };
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  auto load = [&](Stage& st, int gk) {
+    const int k = gk * LS_BK + ak;
+    const bool kok = k < K;  // K % 4 == 0: a float4 is inside or outside as a whole; the tail is zero-filled
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int row = m0 + ar + 32 * i;
+      st.ra[i] = (kok && row < R) ? *reinterpret_cast<const float4*>(a.dg_next + (long long)row * K + k) : zero4;
+    }
+    const int kb = gk * LS_BK + 2 * bj;  // K is even: the pair is inside or outside as a whole
+    const bool bok = wok && kb < K;
+    st.w0 = bok ? a.w_hh[(long long)kb * H + wunit] : 0.f;
+    st.w1 = bok ? a.w_hh[(long long)(kb + 1) * H + wunit] : 0.f;
+  };
+  auto store = [&](const Stage& st) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      unsigned lo[3], hi[3];
+      split3_pair(st.ra[i].x, st.ra[i].y, lo);
+      split3_pair(st.ra[i].z, st.ra[i].w, hi);
+#pragma unroll
+      for (int p = 0; p < 3; ++p)
+        *reinterpret_cast<uint2*>(&Gs[p * LB_PLANE + (ar + 32 * i) * LS_LDW + ak / 2]) = make_uint2(lo[p], hi[p]);
+    }
+    unsigned wd[3];
+    split3_pair(st.w0, st.w1, wd);
+#pragma unroll
+    for (int p = 0; p < 3; ++p) Gs[p * LB_PLANE + (LS_ROWS + bu) * LS_LDW + bj] = wd[p];
+  };
+  auto frag = [&](int row, bf16x8_l (&o)[3]) {
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+      o[p] = __builtin_bit_cast(
+          bf16x8_l, *reinterpret_cast<const u32x4_l*>(&Gs[p * LB_PLANE + row * LS_LDW + 4 * (lane >> 4)]));
+  };
+  auto compute = [&]() {
+    bf16x8_l av[3], bv[3];
+    frag(16 * w + (lane & 15), av);
+    frag(LS_ROWS + (lane & 15), bv);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[1], bv[1], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bv[2], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[2], bv[0], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bv[1], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[1], bv[0], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0], bv[0], acc, 0, 0, 0);
+  };
+  static_assert(LS_DEPTH == 4, "four named stages below");
+  Stage s0, s1, s2, s3;
+  s0.ra[0] = s0.ra[1] = zero4;
+  s0.w0 = s0.w1 = 0.f;
+  s1 = s0;
+  s2 = s0;
+  s3 = s0;
+  if (0 < ng) load(s0, g0);
+  if (1 < ng) load(s1, g0 + 1);
+  if (2 < ng) load(s2, g0 + 2);
+  if (3 < ng) load(s3, g0 + 3);
+  auto step = [&](Stage& st, int kt) {  // kt < ngmax: the same for the whole workgroup
+    if (kt < ng) {
+      store(st);
+      if (kt + LS_DEPTH < ng) load(st, g0 + kt + LS_DEPTH);
+    }
+    __syncthreads();
+    if (kt < ng) compute();
+    __syncthreads();
+  };
+  for (int base = 0; base < ngmax; base += LS_DEPTH) {
+    step(s0, base);
+    if (base + 1 < ngmax) step(s1, base + 1);
+    if (base + 2 < ngmax) step(s2, base + 2);
+    if (base + 3 < ngmax) step(s3, base + 3);
+  }
+  // every k-group parks its sums in its own staging tile (wave w, lane l at (64 w + l) 4 + r)
+  if (a.kt > 0) {  // uniform over the launch
+    *reinterpret_cast<f32x4_l*>(&Gs[(w * 64 + lane) * 4]) = acc;
+    __syncthreads();
+  }
+
+  // the cell, one (row, unit) per thread: lstm_cell_bwd_kernel's fp32 formulas
+  const int lrow = tid >> 4, u = tn * LS_UNITS + (tid & 15), row = m0 + lrow;
+  if (u >= H || row >= R) return;
+  float dh = a.dh_lin ? a.dh_lin[(long long)row * a.ld_dh + u] : 0.f;
+  if (a.kt > 0) {
+    const int slot = ((lrow >> 4) * 64 + ((lrow & 15) >> 2) * 16 + (tid & 15)) * 4 + (lrow & 3);
+    const float* sums = reinterpret_cast<const float*>(lds);
+    float s = sums[slot];
+#pragma unroll
+    for (int k = 1; k < LS_KG; ++k) s += sums[k * LB_GBUF + slot];
+    dh += s;
+  }
+  const long long i = (long long)row * H + u, o = (long long)row * K + u;
+  float dc = a.dc_in ? a.dc_in[i] : 0.f;
+  const float ig = a.act[o], fg = a.act[o + H], cg = a.act[o + 2 * H], og = a.act[o + 3 * H];
+  const float tc = tanhf(a.c_cur[i]);
+  const float d_o = dh * tc * og * (1.f - og);
+  dc += dh * og * (1.f - tc * tc);
+  const float d_i = dc * cg * ig * (1.f - ig);
+  const float d_f = dc * (a.c_prev ? a.c_prev[i] : 0.f) * fg * (1.f - fg);
+  const float d_g = dc * ig * (1.f - cg * cg);
+  a.dgates[o] = d_i;
+  a.dgates[o + H] = d_f;
+  a.dgates[o + 2 * H] = d_g;
+  a.dgates[o + 3 * H] = d_o;
+  a.dc_out[i] = dc * fg;
+}
+
+int lstm_step_launch(const float* pre, long long ld_pre, const float* x, long long ld_x, int M, const float* h_prev,
+                     long long ld_h, const float* c_prev, long long ld_c, const float* w_ih, const float* w_hh,
+                     const float* b_ih, const float* b_hh, int R, int H, float* h_out, float* c_out, float* act_out,
+                     bool train, void* stream) {
   CAPMI_REQUIRE(h_out && c_out && h_out != c_out && R > 0 && H > 0 && M >= 0, CAPMI_EINVAL);
   CAPMI_REQUIRE(M % 4 == 0 && H % 4 == 0, CAPMI_EINVAL);
   CAPMI_REQUIRE(pre || x || h_prev, CAPMI_EINVAL);
@@ -208,6 +376,10 @@ extern "C" int capmi_lstm_step_fwd(const float* pre, long long ld_pre, const flo
                 CAPMI_EINVAL);
   CAPMI_REQUIRE(!c_prev || ld_c >= H, CAPMI_EINVAL);
   CAPMI_REQUIRE(h_out != h_prev && h_out != c_prev && c_out != h_prev && c_out != c_prev, CAPMI_EINVAL);
+  if (train)
+    CAPMI_REQUIRE(act_out && act_out != h_out && act_out != c_out && act_out != pre && act_out != x &&
+                      act_out != h_prev && act_out != c_prev,
+                  CAPMI_EINVAL);
   CAPMI_REQUIRE(cdiv(R, LS_ROWS) <= 65535u, CAPMI_ERANGE);
   LsArgs a{};
   a.pre = pre, a.x = x, a.h_prev = h_prev, a.c_prev = c_prev;
@@ -216,9 +388,56 @@ extern "C" int capmi_lstm_step_fwd(const float* pre, long long ld_pre, const flo
   a.M = M, a.H = H, a.R = R;
   a.kt_x = x ? (int)cdiv(M, LS_BK) : 0;
   a.kt = a.kt_x + (h_prev ? (int)cdiv(H, LS_BK) : 0);
-  a.h_out = h_out, a.c_out = c_out;
-  hipLaunchKernelGGL(lstm_step_kernel, dim3(cdiv(H, LS_UNITS), cdiv(R, LS_ROWS)), dim3(256 * LS_KG), 0,
+  a.h_out = h_out, a.c_out = c_out, a.act_out = act_out;
+  const dim3 grid(cdiv(H, LS_UNITS), cdiv(R, LS_ROWS));
+  if (train)
+    hipLaunchKernelGGL(lstm_step_kernel<true>, grid, dim3(256 * LS_KG), 0, as_stream(stream), a);
+  else
+    hipLaunchKernelGGL(lstm_step_kernel<false>, grid, dim3(256 * LS_KG), 0, as_stream(stream), a);
+  CAPMI_LAUNCH_CHECK();
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int capmi_lstm_step_fwd(const float* pre, long long ld_pre, const float* x, long long ld_x, int M,
+                                   const float* h_prev, long long ld_h, const float* c_prev, long long ld_c,
+                                   const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                                   int R, int H, float* h_out, float* c_out, void* stream) {
+  return lstm_step_launch(pre, ld_pre, x, ld_x, M, h_prev, ld_h, c_prev, ld_c, w_ih, w_hh, b_ih, b_hh, R, H, h_out,
+                          c_out, nullptr, false, stream);
+}
+
+extern "C" int capmi_lstm_step_fwd_train(const float* pre, long long ld_pre, const float* x, long long ld_x, int M,
+                                         const float* h_prev, long long ld_h, const float* c_prev, long long ld_c,
+                                         const float* w_ih, const float* w_hh, const float* b_ih,
+                                         const float* b_hh, int R, int H, float* h_out, float* c_out,
+                                         float* act_out, void* stream) {
+  return lstm_step_launch(pre, ld_pre, x, ld_x, M, h_prev, ld_h, c_prev, ld_c, w_ih, w_hh, b_ih, b_hh, R, H, h_out,
+                          c_out, act_out, true, stream);
+}
+
+extern "C" int capmi_lstm_step_bwd(const float* dh_lin, long long ld_dh, const float* dg_next, const float* w_hh,
+                                   const float* dc_in, const float* act, const float* c_prev, const float* c_cur,
+                                   int R, int H, float* dgates, float* dc_out, void* stream) {
+  CAPMI_REQUIRE(act && c_cur && dgates && dc_out && R > 0 && H > 0, CAPMI_EINVAL);
+  CAPMI_REQUIRE(H % 4 == 0, CAPMI_EINVAL);
+  CAPMI_REQUIRE(!dh_lin || ld_dh >= H, CAPMI_EINVAL);
+  CAPMI_REQUIRE(!dg_next || (w_hh && aligned16(dg_next)), CAPMI_EINVAL);
+  const void* ins[] = {dh_lin, dg_next, w_hh, dc_in, act, c_prev, c_cur};
+  for (const void* p : ins)
+    CAPMI_REQUIRE((const void*)dgates != p && (const void*)dc_out != p, CAPMI_EINVAL);
+  CAPMI_REQUIRE((void*)dgates != (void*)dc_out, CAPMI_EINVAL);
+  CAPMI_REQUIRE(cdiv(R, LS_ROWS) <= 65535u, CAPMI_ERANGE);
+  LbArgs a{};
+  a.dh_lin = dh_lin, a.dg_next = dg_next, a.w_hh = w_hh, a.dc_in = dc_in;
+  a.act = act, a.c_prev = c_prev, a.c_cur = c_cur;
+  a.ld_dh = ld_dh, a.H = H, a.R = R;
+  a.kt = dg_next ? (int)cdiv(4LL * H, LS_BK) : 0;
+  a.dgates = dgates, a.dc_out = dc_out;
+  hipLaunchKernelGGL(lstm_step_bwd_kernel, dim3(cdiv(H, LS_UNITS), cdiv(R, LS_ROWS)), dim3(256 * LS_KG), 0,
                      as_stream(stream), a);
   CAPMI_LAUNCH_CHECK();
   return 0;
 }
+

@@ -6,8 +6,12 @@ Linear), as in the reference. On HIP tensors forward()
 is capmi.baseline_fn.BaselineDecoderFn: the same parameters, hoisted input and
 vocabulary GEMMs, the fused LSTM cell per step and a BPTT backward on the capmi
 kernels. The ResNet-101 encoder (models.encoder.Encoder) runs the capmi kernels
-when given HIP tensors.
+when given HIP tensors. train() on a HIP device runs capmi.baseline_train.
+BaselineTrainStep (one launch per timestep each way, fused CE with ignore_index,
+gradients in place, clamp + Adam, HIP graphs, data parallel); forward() and the
+autograd path stay as they are.
 """
+import os
 import time
 
 import torch
@@ -87,6 +91,9 @@ def train(device, args):
         imgs, captions = zip(*data)
         return torch.stack(imgs, 0), pad_sequence(captions, batch_first=True, padding_value=pad_idx)
 
+    if torch.device(device).type == "cuda" and os.environ.get("CAPMI_BASELINE_STEP", "1") != "0":
+        return _train_on_step(device, args, dataset, pad_idx, collate_fn)
+    # CPU devices, and CAPMI_BASELINE_STEP=0 on the GPU: the reference's autograd loop
     loader = torch.utils.data.DataLoader(dataset, batch_size=args.batch_size, shuffle=True,
                                          num_workers=args.workers, collate_fn=collate_fn)
     encoder = Encoder(args.embed_size)
@@ -139,6 +146,78 @@ def train(device, args):
                         {'epoch_losses': epoch_losses})
     print(f'Model {args.model_name} finished training for {args.epochs} epochs in '
           f'{time.time() - train_start:.4f} seconds.')
+
+
+def _train_on_step(device, args, dataset, pad_idx, collate_fn):
+    """``train`` on a HIP device: the same models, loop and log line on capmi.baseline_train.BaselineTrainStep
+    (fused CE with ignore_index, gradients in place, clamp fused into capmi.optim.Adam, one HIP graph per batch
+    shape unless CAPMI_TRAIN_GRAPH=0). Losses stay on the device and are read every ``print_freq`` batches and
+    at the epoch's end; data-parallel over torchrun ranks when WORLD_SIZE > 1 (rank 0 prints and saves)."""
+    from capmi import dist as cdist
+    from capmi import kernels as K
+    from capmi.baseline_train import BaselineTrainStep
+    from capmi.optim import Adam
+    ctx = cdist.init_from_env(device)
+    device = ctx.device
+    sampler = cdist.sampler_for(dataset, ctx)
+    loader = torch.utils.data.DataLoader(dataset, batch_size=args.batch_size, shuffle=sampler is None,
+                                         sampler=sampler, num_workers=args.workers, collate_fn=collate_fn)
+    encoder = Encoder(args.embed_size)
+    params = BaselineDecoderParams()
+    params.embed_size, params.hidden_size, params.vocab_size = args.embed_size, args.decoder_dim, len(dataset.vocab)
+    decoder = BaselineDecoder(params)
+    if args.use_glove:
+        from embed import load_glove_vectors
+        decoder.load_pretrained_embeddins(load_glove_vectors())
+    decoder.fine_tune_embeddings(on=args.fine_tune_embedding)
+    encoder, decoder = encoder.to(device), decoder.to(device)
+    # every rank starts from rank 0's weights and BN buffers
+    cdist.broadcast_module(encoder, ctx)
+    cdist.broadcast_module(decoder, ctx)
+    # reference :279-282: only the (trainable) embed Linear, since fine_tune() is never called
+    encoder_optimizer = Adam(filter(lambda p: p.requires_grad, encoder.parameters()),
+                             lr=args.encoder_lr) if args.fine_tune_encoder else None
+    decoder_optimizer = Adam(filter(lambda p: p.requires_grad, decoder.parameters()), lr=args.decoder_lr)
+    step = BaselineTrainStep(encoder, decoder, decoder_optimizer, ctx,
+                             graph=os.environ.get("CAPMI_TRAIN_GRAPH", "1") != "0",
+                             encoder_optimizer=encoder_optimizer, ignore_index=pad_idx)
+    train.last_step = step  # (tests: which launch mode ran)
+    decoder.train()
+    encoder.train()
+    train_start = time.time()
+    num_batches = len(loader)
+    epoch_losses = []
+    for epoch in range(args.epochs):
+        if sampler is not None:
+            sampler.set_epoch(epoch)
+        batch_losses, pending = [], []
+        accum_loss, accum_time = AccumulatingMetric(), AccumulatingMetric()
+        start = time.time()
+        for batch_idx, (imgs, captions) in enumerate(loader):
+            imgs, captions = imgs.to(device, non_blocking=True), captions.to(device, non_blocking=True)
+            clip_gradient(decoder_optimizer, args.grad_clip)
+            if encoder_optimizer is not None:
+                clip_gradient(encoder_optimizer, args.grad_clip)
+            pending.append(step(imgs, captions).detach().clone())  # the step's own buffer: the next call reuses it
+            if batch_idx % args.print_freq == 0 or batch_idx == num_batches - 1:
+                torch.cuda.synchronize()
+                K.sk_check()  # stream-K hand-off invariant (raises on a timed-out hand-off)
+                for l in torch.stack(pending).view(-1).tolist():
+                    batch_losses.append(l)
+                    accum_loss.update(l)
+                pending = []
+                accum_time.update(time.time() - start)
+                if ctx.rank == 0 and batch_idx % args.print_freq == 0:
+                    print(f'Epoch {epoch+1}/{args.epochs}, Batch {batch_idx+1}/{num_batches}, '
+                          f'Loss {accum_loss.avg():.4f}, Time: {accum_time.val:.4f}')
+            start = time.time()
+        epoch_losses.append(batch_losses)
+        if ctx.rank == 0:
+            save_checkpoint(args, epoch, encoder, decoder, encoder_optimizer, decoder_optimizer,
+                            {'epoch_losses': epoch_losses})
+    if ctx.rank == 0:
+        print(f'Model {args.model_name} finished training for {args.epochs} epochs in '
+              f'{time.time() - train_start:.4f} seconds.')
 
 
 def _eval_dataset(args):

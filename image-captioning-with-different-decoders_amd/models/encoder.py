@@ -129,6 +129,13 @@ class Encoder(nn.Module):
                          self.embed.out_features, bias=self.embed.bias), 0, 0, K.TILE_64)
         return out
 
+    def pooled_features(self, imgs):
+        """The frozen ResNet's pooled (N, 2048) features of HIP images: what ``embed`` is applied to
+        (capmi.baseline_train runs ``embed`` itself, writing straight into the decoder's step-0 input)."""
+        _check_frozen(self.resnet)
+        feats = self._runner.forward(_ResNetView(self.resnet), imgs.contiguous(), (1, 1), train=self.training)
+        return feats.view(feats.shape[0], -1)
+
     def fine_tune(self, on=True):
         for conv_block in list(self.resnet.children())[5:]:
             for param in conv_block.parameters():

@@ -623,6 +623,45 @@ int capmi_eval_captions_ce(const float* loss_rows, const int* rank, const int* l
                            float* cap_ce, int* cap_top1, int* cap_top5, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Baseline (LSTM) captioner in training (reference models/baseline.py:114-264; csrc/baseline_step.hip,
+ * csrc/baseline_train.hip). New symbols only, nothing existing changed; added without an ABI bump (purely
+ * additive, as the BERT entries below).
+ * ---------------------------------------------------------------------- */
+/* capmi_lstm_step_fwd that also writes act_out [R][4H] (contiguous) = (sig i | sig f | tanh g | sig o), the fp64
+ * activations rounded to fp32, in capmi_lstm_cell_fwd's layout: what a backward step reads. h_out / c_out are
+ * capmi_lstm_step_fwd's bits on the same inputs. Same argument rules; act_out required and distinct from every
+ * other buffer. */
+int capmi_lstm_step_fwd_train(const float* pre, long long ld_pre, const float* x, long long ld_x, int M,
+                              const float* h_prev, long long ld_h, const float* c_prev, long long ld_c,
+                              const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, int R,
+                              int H, float* h_out, float* c_out, float* act_out, void* stream);
+/* One backward-through-time step of that LSTM in one launch:
+ *   dh[r][u] = (dh_lin ? dh_lin[r][u] : 0) + (dg_next ? sum_{k<4H} dg_next[r][k] W_hh[k][u] : 0)
+ * then capmi_lstm_cell_bwd's formulas on act [R][4H], c_prev (NULL = zeros) / c_cur [R][H] and dc_in [R][H]
+ * (NULL = zeros) -> dgates [R][4H] (pre-activation) and dc_out [R][H]. dh_lin has row stride ld_dh >= H, all else
+ * is contiguous; dg_next is step t+1's dgates (NULL at the last step: the launch then does no GEMM), W_hh [4H][H].
+ * fp32-accurate (three-term bf16 split, fp32 accumulation); a row's result depends on that row's inputs and on H
+ * alone. CAPMI_EINVAL unless R, H > 0, H % 4 == 0, act / c_cur / dgates / dc_out given, W_hh given with dg_next,
+ * dg_next 16-byte aligned, and dgates / dc_out distinct from each other and from every input. */
+int capmi_lstm_step_bwd(const float* dh_lin, long long ld_dh, const float* dg_next, const float* w_hh,
+                        const float* dc_in, const float* act, const float* c_prev, const float* c_cur, int R, int H,
+                        float* dgates, float* dc_out, void* stream);
+/* nn.CrossEntropyLoss(ignore_index) over logits (B,T,V), rows r = b*T + t, target = caps[b*L + t + tgt_off]
+ * (tgt_off >= 0, L >= T + tgt_off). The count of live targets stays on the device (graph-replayable):
+ * count[0] (may be NULL) = #{targets != ignore_index}, inv_count[0] = 1 / count (count 0: +inf). */
+int capmi_count_targets(const long long* caps, int B, int T, int L, int tgt_off, long long ignore_index, int* count,
+                        float* inv_count, void* stream);
+/* capmi_ce_fwd_bwd's per-row arithmetic: a live row writes loss_rows[r] = lse - x[target] and (dlogits non-NULL)
+ * (softmax - onehot) * inv_count[0]; an ignored row (target == ignore_index, or outside [0, V): never followed)
+ * writes loss_rows[r] = 0 and an all-zero dlogits row. dlogits row t*B + b when dl_time_major else b*T + t. */
+int capmi_ce_ignore_fwd_bwd(const float* logits, const long long* caps, int B, int T, int L, int V, int tgt_off,
+                            long long ignore_index, const float* inv_count, float* loss_rows, float* dlogits,
+                            int dl_time_major, void* stream);
+/* loss = sum(loss_rows[0:n]) * inv_count[0] -> out[0] (one workgroup, deterministic). No live target: NaN, as
+ * torch. */
+int capmi_loss_finalize_dev(const float* loss_rows, int n, const float* inv_count, float* out, void* stream);
+
+/* ------------------------------------------------------------------------
  * Optimiser (train_utils.py:2-12 clamp + torch.optim.Adam, models/attention.py:352-355,423-430)
  * p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps) with g clamped to +-clip first.
  * step_dev == NULL: bc1 = 1 - beta1^t and bc2_sqrt = sqrt(1 - beta2^t) as passed (host step t);
