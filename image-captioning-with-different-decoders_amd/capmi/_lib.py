@@ -175,6 +175,8 @@ _SIGS = {
     "capmi_resize_normalize_u8": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,
                                   c_vp, c_vp],
     "capmi_resize_taps_max": [c_int, c_int],
+    "capmi_resize_u8_slots": [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_ll, c_vp],
+    "capmi_gather_normalize_u8": [c_vp, c_ll, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp],
     "capmi_split3_bf16": [c_vp, c_ll, c_vp, c_vp],
     "capmi_bn_relu_split3": [c_vp, c_vp, c_vp, c_ll, c_int, c_vp, c_vp],
     "capmi_bert_embed_ln": [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_float, c_vp,

@@ -63,6 +63,7 @@ class BaselineTrainStep:
         self._gcache = {}  # (image shape, caption shape) -> (graph, static inputs); no eviction
         self.graph_cache_size = int(os.environ.get("CAPMI_GRAPH_CACHE", "8"))
         self.counts = {"replay": 0, "eager": 0, "capture": 0}
+        self.capture_error_mode = "global"  # "thread_local" beside a DataLoader's pin-memory thread (AttentionTrainStep)
 
     # ------------------------------------------------------------------ buffers
     def _buffers(self, B, L):
@@ -268,7 +269,7 @@ class BaselineTrainStep:
                 b.copy_(v)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
+        with torch.cuda.graph(g, capture_error_mode=self.capture_error_mode):
             st["loss"] = self._body(st["imgs"], st["caps"], with_update=not self.ctx.distributed)
         # the encoder runner's per-shape workspace cache keeps only the latest shape: hold this one's
         st["pins"] = [getattr(getattr(self.encoder, "_runner", None), "_ws", None), self._ws[tuple(captions.shape)]]

@@ -472,6 +472,40 @@ def resize_normalize_u8(src, offsets, heights, widths, max_h, max_w, OH, OW, mea
          m, s, ptr(tmp), ptr(out), stream())
 
 
+def resize_u8_slots(src, offsets, heights, widths, slot, max_h, max_w, OH, OW, tmp, slots):
+    """The resample of ``resize_normalize_u8`` for n packed images, its uint8 result stored HWC into
+    ``slots[slot[i]]`` (capmi_resize_u8_slots). slot int32 [n] on the device, already validated on the host
+    (capmi.imagepipe); slots uint8 (n_slots, OH, OW, 3) contiguous; tmp uint8 >= n * max_h * OW * 3."""
+    n = heights.numel()
+    _cuda(src, tmp, slots, dtype=torch.uint8)
+    _cuda(offsets, dtype=torch.int64)
+    _cuda(heights, widths, slot, dtype=torch.int32)
+    n_slots = _slot_count(slots, OH, OW)
+    assert offsets.numel() == n and widths.numel() == n and slot.numel() == n and tmp.numel() >= n * max_h * OW * 3
+    call("capmi_resize_u8_slots", ptr(src), ptr(offsets), ptr(heights), ptr(widths), ptr(slot), n, max_h, max_w,
+         OH, OW, ptr(tmp), ptr(slots), n_slots, stream())
+
+
+def gather_normalize_u8(slots, slot, OH, OW, mean, std, out):
+    """out[b] = Normalize(ToTensor(slots[slot[b]])), (B, 3, OH, OW) fp32, bit-equal to ``resize_normalize_u8``
+    on the cached bytes (capmi_gather_normalize_u8). slot int32 [B] on the device, validated on the host."""
+    B = slot.numel()
+    _cuda(slots, dtype=torch.uint8)
+    _cuda(slot, dtype=torch.int32)
+    _cuda(out)
+    n_slots = _slot_count(slots, OH, OW)
+    assert out.is_contiguous() and out.numel() >= B * 3 * OH * OW
+    m = (ctypes.c_float * 3)(*mean)
+    s = (ctypes.c_float * 3)(*std)
+    call("capmi_gather_normalize_u8", ptr(slots), n_slots, ptr(slot), B, OH, OW, m, s, ptr(out), stream())
+
+
+def _slot_count(slots, OH, OW):
+    if not slots.is_contiguous() or slots.numel() % (OH * OW * 3):
+        raise ValueError("slots: contiguous uint8 storage of whole (OH, OW, 3) images")
+    return slots.numel() // (OH * OW * 3)
+
+
 def adaptive_avgpool_nhwc(inp, N, H, W, C, OH, OW, out):
     _cuda(inp, out)
     call("capmi_adaptive_avgpool_nhwc", ptr(inp), N, H, W, C, OH, OW, ptr(out), stream())

@@ -92,6 +92,9 @@ class AttentionTrainStep:
         # optional callable(label) run before each graph capture (bench: graph-node timing), and
         # the labels of the graphs the last call replayed ("enc0"/"dec1"..., or "step")
         self.capture_hook = None
+        # "thread_local" when another thread of the process may call the runtime during a capture: a DataLoader's
+        # pin-memory thread allocates pinned memory, which ends a capture made in the default "global" mode
+        self.capture_error_mode = "global"
         self.replayed = []
         self.schedule = []  # graph segments replayed and collectives issued by the last call, in order
         self._segs = None  # data-parallel graph mode: (graphs, the bucket label ending each)
@@ -396,7 +399,7 @@ class AttentionTrainStep:
             g = torch.cuda.CUDAGraph()
             if self.capture_hook is not None:
                 self.capture_hook(f"enc{slot}")
-            with torch.cuda.graph(g):
+            with torch.cuda.graph(g, capture_error_mode=self.capture_error_mode):
                 self._encode_into(st["imgs"], feats[slot], dup)
             st["g_enc"] = g
             st["feats"] = feats[slot]  # the graphs hold raw pointers: keep the buffer alive
@@ -405,7 +408,7 @@ class AttentionTrainStep:
             with self._feats_from(st):
                 if upd:
                     g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
+                    with torch.cuda.graph(g, capture_error_mode=self.capture_error_mode):
                         st["loss"] = self._dec_body(feats[slot], st["caps"], st["lens"], with_update=True,
                                                     dup=dup)
                     st["g_dec"] = g
@@ -414,14 +417,14 @@ class AttentionTrainStep:
                     # is issued between the replays and runs beside the backward-through-time graph
                     st["loss"], st["g_dec"], st["g_dec2"] = self._capture_split(
                         lambda cut: self._dec_body(feats[slot], st["caps"], st["lens"], with_update=False, on_fc=cut,
-                                                   dup=dup))
+                                                   dup=dup), self.capture_error_mode)
         torch.cuda.synchronize()
         pg[0]["pins"] = self._pins()
         self.counts["capture"] += 1
         return pg
 
     @staticmethod
-    def _capture_segments(body):
+    def _capture_segments(body, mode="global"):
         """Capture ``body(cut)`` into a chain of HIP graphs sharing one memory pool: every
         ``cut(label)`` ends the graph being captured and starts the next. Returns (body's result,
         [graphs], [the label of the cut that ended each graph; None for the last])."""
@@ -436,10 +439,10 @@ class AttentionTrainStep:
             graphs[-1].capture_end()
             labels.append(label)
             graphs.append(torch.cuda.CUDAGraph())
-            graphs[-1].capture_begin(pool=pool)
+            graphs[-1].capture_begin(pool=pool, capture_error_mode=mode)
 
         with torch.cuda.stream(cs):
-            graphs[0].capture_begin(pool=pool)
+            graphs[0].capture_begin(pool=pool, capture_error_mode=mode)
             out = body(cut)
             graphs[-1].capture_end()
             labels.append(None)
@@ -447,7 +450,7 @@ class AttentionTrainStep:
         return out, graphs, labels
 
     @staticmethod
-    def _capture_split(body):
+    def _capture_split(body, mode="global"):
         """Capture ``body(cut)`` into two HIP graphs sharing one memory pool: the first ends where
         body calls ``cut()``. Returns (body's result, graph 1, graph 2)."""
         g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
@@ -460,11 +463,11 @@ class AttentionTrainStep:
 
         def cut():
             g1.capture_end()
-            g2.capture_begin(pool=pool)
+            g2.capture_begin(pool=pool, capture_error_mode=mode)
             cut_done.append(True)
 
         with torch.cuda.stream(cs):
-            g1.capture_begin(pool=pool)
+            g1.capture_begin(pool=pool, capture_error_mode=mode)
             out = body(cut)
             if not cut_done:  # body never cut: everything is in graph 1, graph 2 stays empty
                 cut()
@@ -669,13 +672,14 @@ class AttentionTrainStep:
             self.capture_hook("step")
         if upd:
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
+            with torch.cuda.graph(g, capture_error_mode=self.capture_error_mode):
                 st["loss"] = self._body(st["imgs"], st["caps"], st["lens"], with_update=True)
             self._segs = None
         else:
             # data parallel: segments cut where buckets become final (fc / decoder, layer4, layer3, layer2)
             st["loss"], graphs, labels = self._capture_segments(
-                lambda cut: self._body(st["imgs"], st["caps"], st["lens"], with_update=False, cut=cut))
+                lambda cut: self._body(st["imgs"], st["caps"], st["lens"], with_update=False, cut=cut),
+                self.capture_error_mode)
             g = graphs[0]
             self._segs = (graphs, labels)
         st["pins"] = self._pins()

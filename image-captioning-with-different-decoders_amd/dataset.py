@@ -7,6 +7,12 @@ the transform of the PIL RGB image, as in the reference. Without one (the MI355X
 decoded (H, W, 3) uint8 array: the loader packs those (capmi.imagepipe.PackedImages) and the GPU
 applies Resize/ToTensor/Normalize bit-identically to torchvision's PIL transform.
 
+COCODataset(..., return_image_key=True) (the device image cache, capmi.imagepipe.DeviceImageCache): a train-mode
+item without a transform is (image or None, caption, key). `key` is the image's index in `img_ids`; `present`
+is a uint8 flag per image in shared memory, which the training process sets once the image is in the cache, and
+an item whose flag is set skips the JPEG decode and carries None. DataLoader workers see flags set after they
+were started. Flags are only ever set, never cleared.
+
 pycocotools and nltk are used when importable; otherwise capmi.coco.COCO (the captions JSON) and
 capmi.text.word_tokenize (Treebank rules) stand in for them.
 """
@@ -28,7 +34,7 @@ def _coco(anno_file):
 
 
 class COCODataset(data.Dataset):
-    def __init__(self, mode, img_transform=None, caption_max_len=50, vocab=None):
+    def __init__(self, mode, img_transform=None, caption_max_len=50, vocab=None, return_image_key=False):
         assert mode in ['train', 'val']
         self.mode = mode
         self.img_transform = img_transform
@@ -39,6 +45,10 @@ class COCODataset(data.Dataset):
         self.coco = _coco(self.anno_file)
         self.img_ids = list(sorted(self.coco.imgs.keys()))
         self.caption_img_mappings = self._build_caption_img_mappings()
+        self.return_image_key = bool(return_image_key) and mode == 'train' and img_transform is None
+        if self.return_image_key:
+            self._key_of = {img_id: k for k, img_id in enumerate(self.img_ids)}
+            self.present = torch.zeros(len(self.img_ids), dtype=torch.uint8).share_memory_()
 
     def _build_caption_img_mappings(self):
         mappings = []
@@ -72,6 +82,10 @@ class COCODataset(data.Dataset):
     def __getitem__(self, idx):
         mapping = self.caption_img_mappings[idx]
         caption, img_id = mapping['caption'], mapping['img_id']
+        if self.return_image_key:
+            key = self._key_of[img_id]
+            img = None if self.present[key] else self._get_transformed_img(img_id)
+            return img, self._numericalize_caption(caption), key
         img = self._get_transformed_img(img_id)
         caption = self._numericalize_caption(caption)
         if self.mode == 'train':

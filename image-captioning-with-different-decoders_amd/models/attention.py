@@ -127,12 +127,17 @@ class AttentionDecoder(nn.Module):
 # ======================================================================================
 # training (reference :287-452)
 # ======================================================================================
-def _train_dataset(args):
+def _train_dataset(args, device=None):
+    """The training set of train() (here and in models.baseline): synthetic, or COCO without a transform
+    (decoded uint8 images, resized on the GPU), with image keys when --image_cache_gb asks for the device
+    image cache on a HIP `device`."""
     from capmi.data import SyntheticCOCO, synthetic_requested
     if synthetic_requested(args):
         return SyntheticCOCO.from_args(args)
+    from capmi.imagepipe import image_cache_requested
     from dataset import COCODataset  # real COCO path (needs pycocotools, nltk, images)
-    return COCODataset(mode='train', caption_max_len=args.max_caption_length)
+    return COCODataset(mode='train', caption_max_len=args.max_caption_length,
+                       return_image_key=device is not None and image_cache_requested(args, device))
 
 
 def _build_models(args, vocab, device):
@@ -202,31 +207,35 @@ def train(device, args):
     GEMMs, fused CE + regulariser, gradients written in place, clamp fused into
     Adam); ``loss.item()`` syncs only every ``print_freq`` batches; data-parallel
     over torchrun ranks when WORLD_SIZE > 1 (gradient all-reduce over RCCL);
-    checkpoints hold state_dicts (Q13)."""
+    checkpoints hold state_dicts (Q13). ``args.image_cache_gb`` > 0 (HIP device, real COCO): the
+    resized uint8 images stay on the device and each JPEG is decoded once per run
+    (capmi.imagepipe.DeviceImageCache; the same image tensors, bit for bit)."""
     from capmi import dist as cdist
+    from capmi.imagepipe import ImageFeeder, collate_images, image_cache_for
     from capmi.train_step import AttentionTrainStep
 
     ctx = cdist.init_from_env(device)
     device = ctx.device
-    dataset = _train_dataset(args)
+    dataset = _train_dataset(args, device)
     pad_idx = dataset.vocab(PAD_TOKEN)
 
     def collate_fn(data):
         from torch.nn.utils.rnn import pad_sequence
-        imgs, captions = zip(*data)
-        if isinstance(imgs[0], torch.Tensor):
-            imgs = torch.stack(imgs, dim=0)
-        else:  # decoded uint8 images (COCODataset without a transform): resized on the GPU
-            from capmi.imagepipe import PackedImages
-            imgs = PackedImages(list(imgs), pin=False)
+        imgs, captions, *keys = zip(*data)
+        # tensors are stacked; decoded uint8 images (COCODataset without a transform) are packed and resized
+        # on the GPU, with their keys when the image cache is on
+        imgs = collate_images(imgs, *keys)
         captions = pad_sequence(captions, batch_first=True, padding_value=pad_idx)
         caption_lengths = [len(caption) for caption in captions]  # after padding (Q1)
         return imgs, captions, caption_lengths
 
     sampler = cdist.sampler_for(dataset, ctx)
+    # with the image cache the workers live for the whole run (they read the dataset's shared `present` flags):
+    # later epochs then start no processes, which is all the host would have left to do in them
     train_loader = torch.utils.data.DataLoader(
         dataset=dataset, batch_size=args.batch_size, shuffle=sampler is None, sampler=sampler,
-        num_workers=args.workers, collate_fn=collate_fn, pin_memory=True)
+        num_workers=args.workers, collate_fn=collate_fn, pin_memory=True,
+        persistent_workers=args.workers > 0 and getattr(dataset, "return_image_key", False))
 
     encoder, decoder, start_epoch, metrics, opt_state, enc_opt_state = _build_models(args, dataset.vocab, device)
     encoder = encoder.to(device)
@@ -257,12 +266,15 @@ def train(device, args):
                               graph=on_gpu and os.environ.get("CAPMI_TRAIN_GRAPH", "1") != "0",
                               encoder_optimizer=encoder_optimizer)
     train.last_step = step  # (tests: which launch mode ran)
+    if args.workers > 0:  # the loader's pin-memory thread allocates while a step is being captured
+        step.capture_error_mode = "thread_local"
 
     decoder.train()
     encoder.train()
     num_batches = len(train_loader)
     epoch_losses = metrics.get('epoch_losses', [])
-    gpu_tf = None
+    feed = ImageFeeder(device, image_cache_for(args, dataset, device, args.batch_size))
+    train.last_image_cache = feed.cache  # (tests: its stats)
     for epoch in range(start_epoch, args.epochs):
         if sampler is not None:
             sampler.set_epoch(epoch)
@@ -272,13 +284,7 @@ def train(device, args):
         start = time.time()
         pending = []
         for batch_idx, (imgs, captions, caption_lengths) in enumerate(train_loader):
-            if isinstance(imgs, torch.Tensor):
-                imgs = imgs.to(device, non_blocking=True)
-            else:  # PackedImages: Resize + ToTensor + Normalize on the GPU (capmi.imagepipe)
-                if gpu_tf is None:
-                    from capmi.imagepipe import GpuImageTransform
-                    gpu_tf = GpuImageTransform(device)
-                imgs = gpu_tf(imgs)
+            imgs = feed(imgs)  # to the device; PackedImages: Resize + ToTensor + Normalize there (capmi.imagepipe)
             captions = captions.to(device, non_blocking=True)
             clip_gradient(decoder_optimizer, args.grad_clip)
             if encoder_optimizer is not None:

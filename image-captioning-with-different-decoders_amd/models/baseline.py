@@ -9,7 +9,9 @@ kernels. The ResNet-101 encoder (models.encoder.Encoder) runs the capmi kernels
 when given HIP tensors. train() on a HIP device runs capmi.baseline_train.
 BaselineTrainStep (one launch per timestep each way, fused CE with ignore_index,
 gradients in place, clamp + Adam, HIP graphs, data parallel); forward() and the
-autograd path stay as they are.
+autograd path stay as they are. Real COCO on that path goes through the loader of the attention train()
+(capmi.imagepipe: packed uint8 images, GPU Resize/ToTensor/Normalize, the device image cache with
+--image_cache_gb).
 """
 import os
 import time
@@ -78,20 +80,21 @@ class BaselineDecoder(nn.Module):
 
 def train(device, args):
     """Reference :114-264 (CE with ignore_index=PAD against the captions incl. <start>)."""
-    from capmi.data import SyntheticCOCO, synthetic_requested
+    from capmi.imagepipe import collate_images
+    from models.attention import _train_dataset
     from torch.nn.utils.rnn import pad_sequence
-    if synthetic_requested(args):
-        dataset = SyntheticCOCO.from_args(args)
-    else:
-        from dataset import COCODataset
-        dataset = COCODataset(mode='train', caption_max_len=args.max_caption_length)
+    on_step = torch.device(device).type == "cuda" and os.environ.get("CAPMI_BASELINE_STEP", "1") != "0"
+    # on the step, as the attention train(): COCO images stay uint8 and are resized on the GPU, through the device
+    # image cache when args.image_cache_gb > 0
+    dataset = _train_dataset(args, device if on_step else None)
     pad_idx = dataset.vocab(PAD_TOKEN)
 
     def collate_fn(data):
-        imgs, captions = zip(*data)
-        return torch.stack(imgs, 0), pad_sequence(captions, batch_first=True, padding_value=pad_idx)
+        imgs, captions, *keys = zip(*data)
+        imgs = collate_images(imgs, *keys) if on_step else torch.stack(imgs, 0)
+        return imgs, pad_sequence(captions, batch_first=True, padding_value=pad_idx)
 
-    if torch.device(device).type == "cuda" and os.environ.get("CAPMI_BASELINE_STEP", "1") != "0":
+    if on_step:
         return _train_on_step(device, args, dataset, pad_idx, collate_fn)
     # CPU devices, and CAPMI_BASELINE_STEP=0 on the GPU: the reference's autograd loop
     loader = torch.utils.data.DataLoader(dataset, batch_size=args.batch_size, shuffle=True,
@@ -156,12 +159,21 @@ def _train_on_step(device, args, dataset, pad_idx, collate_fn):
     from capmi import dist as cdist
     from capmi import kernels as K
     from capmi.baseline_train import BaselineTrainStep
+    from capmi.data import synthetic_requested
+    from capmi.imagepipe import ImageFeeder, image_cache_for
     from capmi.optim import Adam
     ctx = cdist.init_from_env(device)
     device = ctx.device
     sampler = cdist.sampler_for(dataset, ctx)
+    # as in the attention train(): packed COCO pixels are uploaded from pinned memory, and with the image cache
+    # the workers live for the whole run
+    pin = not synthetic_requested(args)
+    keep = args.workers > 0 and getattr(dataset, "return_image_key", False)
     loader = torch.utils.data.DataLoader(dataset, batch_size=args.batch_size, shuffle=sampler is None,
-                                         sampler=sampler, num_workers=args.workers, collate_fn=collate_fn)
+                                         sampler=sampler, num_workers=args.workers, collate_fn=collate_fn,
+                                         pin_memory=pin, persistent_workers=keep)
+    feed = ImageFeeder(device, image_cache_for(args, dataset, device, args.batch_size))
+    train.last_image_cache = feed.cache  # (tests: its stats)
     encoder = Encoder(args.embed_size)
     params = BaselineDecoderParams()
     params.embed_size, params.hidden_size, params.vocab_size = args.embed_size, args.decoder_dim, len(dataset.vocab)
@@ -182,6 +194,8 @@ def _train_on_step(device, args, dataset, pad_idx, collate_fn):
                              graph=os.environ.get("CAPMI_TRAIN_GRAPH", "1") != "0",
                              encoder_optimizer=encoder_optimizer, ignore_index=pad_idx)
     train.last_step = step  # (tests: which launch mode ran)
+    if pin and args.workers > 0:  # the loader's pin-memory thread allocates while a step is being captured
+        step.capture_error_mode = "thread_local"
     decoder.train()
     encoder.train()
     train_start = time.time()
@@ -194,7 +208,7 @@ def _train_on_step(device, args, dataset, pad_idx, collate_fn):
         accum_loss, accum_time = AccumulatingMetric(), AccumulatingMetric()
         start = time.time()
         for batch_idx, (imgs, captions) in enumerate(loader):
-            imgs, captions = imgs.to(device, non_blocking=True), captions.to(device, non_blocking=True)
+            imgs, captions = feed(imgs), captions.to(device, non_blocking=True)
             clip_gradient(decoder_optimizer, args.grad_clip)
             if encoder_optimizer is not None:
                 clip_gradient(encoder_optimizer, args.grad_clip)

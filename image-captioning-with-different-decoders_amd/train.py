@@ -5,7 +5,8 @@
 
 Flags, defaults and the argparse ``type=bool`` quirk (any non-empty string is True,
 Q10) are the reference's. Added: ``--synthetic`` (COCO-shaped synthetic data; the COCO
-pipeline is not part of this build) and data parallelism from torchrun's env.
+pipeline is not part of this build), data parallelism from torchrun's env, and ``--image_cache_gb``
+(real COCO on the GPU: the resized uint8 images stay in device memory, each JPEG is decoded once per run).
 """
 import argparse
 import os
@@ -54,6 +55,9 @@ def parse_args(argv=None):
     parser.add_argument('--bert_path', type=str, default=None,
                         help='local BERT checkpoint directory (pytorch_model.bin or model.safetensors, config.json, '
                              'vocab.txt) for --use_bert; never fetched by name.')
+    parser.add_argument('--image_cache_gb', type=float, default=0,
+                        help='GB of device memory for resized uint8 COCO images (150,528 B each; 12.5 GB holds '
+                             'train2014): each JPEG is then decoded once per run. 0: off.')
     return parser.parse_args(argv)
 
 

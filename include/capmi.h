@@ -274,6 +274,20 @@ int capmi_resize_normalize_u8(const unsigned char* src, const long long* offsets
                               const float* std, void* tmp, float* out, void* stream);
 /* taps per output index of that resample (2*ceil(max(1, in/out)) + 1); host-only helper */
 int capmi_resize_taps_max(int in_size, int out_size);
+/* Device image cache. The same resample for n packed images, but the vertical pass stores its
+ * rounded uint8 result, HWC, into slots + slot[i] * OH*OW*3: the bytes capmi_resize_normalize_u8 divides by 255.
+ * slot: n device ints; slots: n_slots * OH*OW*3 bytes; tmp: n * max_h * OW * 3 bytes. An image whose slot is
+ * outside [0, n_slots) is written nowhere. Same limits as capmi_resize_normalize_u8; n == 0 launches nothing. */
+int capmi_resize_u8_slots(const unsigned char* src, const long long* offsets, const int* heights,
+                          const int* widths, const int* slot, int n, int max_h, int max_w, int OH, int OW,
+                          void* tmp, unsigned char* slots, long long n_slots, void* stream);
+/* ToTensor + Normalize of cached images: out[b][c][y][x] = ((float)slots[slot[b]][y][x][c] / 255.f - mean[c]) /
+ * std[c], the expression of capmi_resize_normalize_u8 (bit-equal to it). slot: B device ints; mean/std: 3 HOST
+ * floats each; out: (B, 3, OH, OW) fp32. An image whose slot is outside [0, n_slots) is neither read nor written.
+ * With OH*OW % 4 == 0, slots 4-B and out 16-B aligned, a lane converts four pixels (three dword loads, one 16-B
+ * store per channel plane); any other shape or alignment runs one pixel per lane. B <= 65535. */
+int capmi_gather_normalize_u8(const unsigned char* slots, long long n_slots, const int* slot, int B, int OH,
+                              int OW, const float* mean, const float* std, float* out, void* stream);
 /* Bottleneck tail: out = relu(y*s + b + (res_scale ? res*rs + rb : res)), NHWC, C % 4 == 0 */
 int capmi_bn_add_relu(const float* y, const float* s, const float* b, const float* res,
                       const float* res_scale, const float* res_shift, float* out, long long rows,
