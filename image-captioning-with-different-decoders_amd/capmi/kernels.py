@@ -721,6 +721,22 @@ def beam_advance(parent, word, top, live, B, k, D, end_idx, step, h_src, c_src, 
 
 
 # --------------------------------------------------------------------------------------
+# sampled decoding (csrc/sample.hip): one launch draws the next token of every alive row
+# --------------------------------------------------------------------------------------
+def sample_step(logits, R, V, u, temperature, top_k, end_idx, step, alive, prev, tokens, logp, rows_live):
+    """logits (R, V) rows (row stride = logits.stride(0)); u (R,) uniforms of this step; tokens / logp: row
+    ``step`` of the caller's (T, R) tables. temperature == 0: greedy. See capmi_sample_step in capmi.h."""
+    _cuda(logits, u, logp)
+    _cuda(alive, tokens, rows_live, dtype=torch.int32)
+    _cuda(prev, dtype=torch.int64)
+    assert logits.dim() == 2 and logits.stride(1) == 1 and logits.size(0) >= R and logits.size(1) == V
+    assert min(x.numel() for x in (u, alive, prev, tokens, logp)) >= R and rows_live.numel() >= 1
+    assert all(x.is_contiguous() for x in (u, alive, prev, tokens, logp))
+    call("capmi_sample_step", ptr(logits), logits.stride(0) if R > 1 else V, R, V, ptr(u), float(temperature),
+         int(top_k), int(end_idx), int(step), ptr(alive), ptr(prev), ptr(tokens), ptr(logp), ptr(rows_live), stream())
+
+
+# --------------------------------------------------------------------------------------
 # teacher-forced validation (csrc/eval.hip): lens[b] = caption b's own decode length, any order
 # --------------------------------------------------------------------------------------
 def eval_rows(logits, caps, B, T, L, V, lens, loss_rows, pred, rank=None):

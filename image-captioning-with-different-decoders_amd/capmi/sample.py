@@ -1,0 +1,248 @@
+"""Sampled caption rollouts on the capmi kernels: the third decode mode beside teacher-forced evaluation
+(capmi.evalpass, capmi.baseline_eval) and beam search (capmi.beam).
+
+``BatchedSampler`` draws ``num_samples`` captions per image from the attention decoder's own distribution
+(temperature and top-k sampling, or the greedy rollout at temperature 0) and records the log-probability of
+every token it emits. The recurrence is ``BatchedBeamSearch``'s, on the same kernels; the sampling stage is one
+launch per step (``capmi_sample_step``, csrc/sample.hip) and all randomness is one table of uniforms drawn
+before the loop, so every draw can be reproduced: sample j of image i at step t uses ``uniforms[t, i*n + j]``
+and nothing else. ``BaselineBatchedSampler`` is the same for the baseline (LSTM) captioner.
+
+The reference project has no sampler; the semantics of a draw are stated at ``capmi_sample_step`` in capmi.h.
+"""
+import torch
+
+from . import kernels as K
+from ._lib import CAPMI_A_KMAJOR as AK, CAPMI_B_NMAJOR_W as BW
+from .beam import BeamSearch
+
+KEEP_LOGITS_MAX_BYTES = 256 << 20
+
+
+def _check_args(num_samples, temperature, top_k):
+    n, temp, top_k = int(num_samples), float(temperature), int(top_k)
+    if n < 1:
+        raise ValueError("num_samples must be >= 1")
+    if not temp >= 0:
+        raise ValueError("temperature must be >= 0 (0: greedy)")
+    if top_k < 0:
+        raise ValueError("top_k must be >= 0 (0: the whole vocabulary)")
+    return n, temp, top_k
+
+
+class _Rollout:
+    """What both samplers share: the uniforms, the per-row state in one int32 buffer, the ``sample_step`` call,
+    the ``sync_every`` stop test and the rebuild of the sequences on the host."""
+
+    def _begin(self, dev, B, V, max_steps, seed, uniforms, keep_logits, sync_every):
+        n = self.n
+        self.R = R = B * n
+        self.T = T = int(max_steps) + 1
+        self.sync_every = max(1, int(sync_every))
+        if uniforms is None:
+            gen = torch.Generator(device=dev)
+            if seed is None:
+                gen.seed()
+            else:
+                gen.manual_seed(int(seed))
+            uniforms = torch.rand(T, R, generator=gen, device=dev, dtype=torch.float32)
+        else:
+            if tuple(uniforms.shape) != (T, R):
+                raise ValueError(f"uniforms must be (max_steps + 1, B * num_samples) = ({T}, {R})")
+            uniforms = uniforms.to(device=dev, dtype=torch.float32).contiguous()
+        self.u = uniforms
+        self.last_logits = None
+        if keep_logits:
+            if T * R * V * 4 > KEEP_LOGITS_MAX_BYTES:
+                raise ValueError("keep_logits: the (T, R, V) logits would take more than 256 MB")
+            self.last_logits = torch.zeros(T, R, V, device=dev, dtype=torch.float32)
+        else:
+            self._logits = torch.empty(R, V, device=dev, dtype=torch.float32)
+        # tokens (T, R) | logp (T, R) as float bits | alive (R) | rows_live (1): one copy brings it to the host
+        self.state = torch.zeros(2 * T * R + R + 1, dtype=torch.int32, device=dev)
+        self.tokens = self.state[:T * R].view(T, R)
+        self.logp = self.state[T * R:2 * T * R].view(torch.float32).view(T, R)
+        self.alive = self.state[2 * T * R:2 * T * R + R]
+        self.rows_live = self.state[2 * T * R + R:]
+        self.tokens.fill_(-1)
+        self.alive.fill_(1)
+        self.rows_live.fill_(R)
+        self.steps = self.syncs = 0
+
+    def _logits_at(self, t_):
+        return self._logits if self.last_logits is None else self.last_logits[t_]
+
+    def _draw(self, logits, t_, V, end_idx, prev):
+        """the step's sampling launch; True when the ``sync_every`` read finds every row finished"""
+        K.sample_step(logits, self.R, V, self.u[t_], self.temperature, self.top_k, end_idx, t_, self.alive, prev,
+                      self.tokens[t_], self.logp[t_], self.rows_live)
+        self.steps += 1
+        if self.steps % self.sync_every == 0 and self.steps < self.T:
+            self.syncs += 1
+            return int(self.rows_live.item()) == 0
+        return False
+
+    def _finish(self, B, start_idx, end_idx):
+        """list of B lists of n dicts (without alphas), and per row the number of tokens it emitted"""
+        T, R, n = self.T, self.R, self.n
+        host = self.state.cpu()
+        self.syncs += 1
+        tok = host[:T * R].view(T, R).t().tolist()
+        lp = host[T * R:2 * T * R].view(torch.float32).view(T, R).t().tolist()
+        out, counts = [], []
+        for i in range(B):
+            per = []
+            for j in range(n):
+                r = i * n + j
+                words, finished = [], False
+                for t_ in range(self.steps):
+                    words.append(tok[r][t_])
+                    if tok[r][t_] == end_idx:
+                        finished = True
+                        break
+                tl = lp[r][:len(words)]
+                per.append({"seq": [start_idx] + words if finished else words, "token_logp": tl,
+                            "logp": float(sum(tl)), "finished": finished, "alphas": []})
+                counts.append(len(words))
+            out.append(per)
+        self.last_stats = {"steps": self.steps, "host_syncs": self.syncs}
+        return out, counts
+
+
+class BatchedSampler(_Rollout):
+    """``num_samples`` sampled captions per image from the attention decoder, B images per call. Rows i*n ..
+    i*n+n-1 of every per-step tensor belong to image i; features and ``enc_att`` features exist once per image
+    (``capmi_beam_att_fwd`` with all n rows of every image live). Rows are not compacted: a row that has
+    emitted END keeps running through the recurrence and ``capmi_sample_step`` ignores it. No host sync in the
+    loop but the read of the count of unfinished rows every ``sync_every`` steps."""
+
+    def __init__(self, decoder, num_samples=1, temperature=1.0, top_k=0):
+        self.n, self.temperature, self.top_k = _check_args(num_samples, temperature, top_k)
+        if self.n > 16:
+            raise ValueError("num_samples must be <= 16 (the rows capmi_beam_att_fwd serves per image)")
+        self.dec = decoder
+        self.last_stats = None
+        self.last_logits = None
+
+    _params = BeamSearch._params
+
+    @torch.no_grad()
+    def sample(self, encoder_out, start_idx, end_idx, max_steps=50, seed=None, uniforms=None, return_alphas=False,
+               keep_logits=False, sync_every=8):
+        """encoder_out: (B, S, S, E) or (B, P, E). ``uniforms``: (max_steps + 1, B * num_samples) fp32 in [0, 1)
+        (default: torch.rand on the device from a generator seeded with ``seed``). Returns a list of B lists of
+        num_samples dicts: ``seq`` ([start, ..., end] when finished, else the max_steps + 1 tokens drawn),
+        ``token_logp`` (one per emitted token), ``logp`` (their sum), ``finished``, ``alphas`` ((emitted + 1, S,
+        S) or (emitted + 1, P) nested lists, a row of ones first, like beam search's; [] without
+        ``return_alphas``). ``keep_logits``: every step's (R, V) logits stay in ``last_logits`` (T, R, V) on
+        the device. ``last_stats`` = steps run and host syncs taken."""
+        if self.dec.use_bert:
+            raise NotImplementedError("sampling with BERT features (as beam search)")
+        p = self._params()
+        dev = encoder_out.device
+        B, E = encoder_out.size(0), encoder_out.size(-1)
+        enc = encoder_out.reshape(B, -1, E).contiguous().float()
+        P, n = enc.size(1), self.n
+        R = B * n
+        A, D = p["W_ea"].shape[0], p["W_hh"].shape[1]
+        M, V = p["emb"].shape[1], p["W_fc"].shape[0]
+        X = M + E
+        self._begin(dev, B, V, max_steps, seed, uniforms, keep_logits, sync_every)
+        T = self.T
+        f = dict(device=dev, dtype=torch.float32)
+        # per batch: att_enc and the initial state, once per image
+        att_enc = torch.empty(B * P, A, **f)
+        K.gemm(K.problem(B * P, A, E, enc, E, p["W_ea"], E, att_enc, A, bias=p["b_ea"]), AK, BW, K.TILE_64)
+        mean = torch.empty(B, E, **f)
+        K.mean_rows(enc, B, P, E, mean)
+        h0, c0 = torch.empty(B, D, **f), torch.empty(B, D, **f)
+        K.gemm([K.problem(B, D, E, mean, E, p["W_h"], E, h0, D, bias=p["b_h"]),
+                K.problem(B, D, E, mean, E, p["W_c"], E, c0, D, bias=p["b_c"])], AK, BW, K.TILE_64)
+        h = h0.repeat_interleave(n, 0).contiguous()
+        c = c0.repeat_interleave(n, 0).contiguous()
+        xin = torch.zeros(R, X, **f)
+        p_ad, p_gate = torch.empty(R, A, **f), torch.empty(R, E, **f)
+        p_hh, p_x = torch.empty(R, 4 * D, **f), torch.empty(R, 4 * D, **f)
+        e_ws = torch.empty(R, P, **f)
+        act, h2, c2 = torch.empty(R, 4 * D, **f), torch.empty(R, D, **f), torch.empty(R, D, **f)
+        alphas = torch.zeros(T, R, P, **f) if return_alphas else None
+        live = torch.full((B,), n, dtype=torch.int32, device=dev)
+        prev = torch.full((R,), start_idx, dtype=torch.int64, device=dev)
+
+        for t_ in range(T):
+            K.embed_gather(p["emb"], prev, R, 1, 1, xin, X)
+            K.gemm([K.problem(R, A, D, h, D, p["W_da"], D, p_ad, A),
+                    K.problem(R, E, D, h, D, p["W_fb"], D, p_gate, E),
+                    K.problem(R, 4 * D, D, h, D, p["W_hh"], D, p_hh, 4 * D)], AK, BW, K.TILE_64)
+            K.beam_att_fwd(enc, att_enc, p_ad, 1, 0, p["b_da"], p["wf"], p["bf"], p_gate, 1, 0, p["b_fb"], live,
+                           B, n, P, A, E, e_ws, alpha_out=alphas[t_] if return_alphas else None,
+                           x_out=xin[:, M:], ld_x=X)
+            K.gemm(K.problem(R, 4 * D, X, xin, X, p["W_ih"], X, p_x, 4 * D, bias=p["b_ih"], bias2=p["b_hh"]),
+                   AK, BW, K.TILE_64)
+            K.lstm_cell_fwd(p_x, 1, 0, None, p_hh, 1, 0, c, R, D, h2, c2, act)
+            logits = self._logits_at(t_)
+            K.gemm(K.problem(R, V, D, h2, D, p["W_fc"], D, logits, V, bias=p["b_fc"]), AK, BW, K.TILE_64)
+            h, h2, c, c2 = h2, h, c2, c  # every row carries its own state on: nothing to gather
+            if self._draw(logits, t_, V, end_idx, prev):
+                break
+        out, counts = self._finish(B, start_idx, end_idx)
+        if return_alphas:
+            al_h = alphas.cpu()
+            self.last_stats["host_syncs"] += 1
+            for r, cnt in enumerate(counts):
+                al = torch.cat([torch.ones(1, P), al_h[:cnt, r]], 0)
+                if encoder_out.dim() == 4:  # (emitted + 1, S, S) like beam search's
+                    al = al.view(-1, encoder_out.size(1), encoder_out.size(2))
+                out[r // n][r % n]["alphas"] = al.tolist()
+        return out
+
+
+class BaselineBatchedSampler(_Rollout):
+    """The same rollouts for the baseline (LSTM) captioner, on the recurrence of ``BaselineBatchedBeamSearch``:
+    the state after feeding the image feature to the LSTM from a zero state is the initial (h, c) of all n rows
+    of an image, then per step embed_gather, capmi_lstm_step_fwd, the R x V x H GEMM and capmi_sample_step.
+    It returns no alphas."""
+
+    def __init__(self, decoder, num_samples=1, temperature=1.0, top_k=0):
+        self.n, self.temperature, self.top_k = _check_args(num_samples, temperature, top_k)
+        self.dec = decoder
+        self.last_stats = None
+        self.last_logits = None
+
+    @torch.no_grad()
+    def sample(self, img_features, start_idx, end_idx, max_steps=50, seed=None, uniforms=None, keep_logits=False,
+               sync_every=8):
+        """img_features (B, M): the encoder's output. Returns what ``BatchedSampler.sample`` returns, every
+        ``alphas`` empty."""
+        from .baseline_eval import STEP_FUSED, lstm_step
+        dec = self.dec
+        if not img_features.is_cuda:
+            raise RuntimeError("capmi baseline decoder path needs HIP tensors")
+        dev = img_features.device
+        feats = img_features.contiguous().float()
+        B, n = feats.size(0), self.n
+        R = B * n
+        M, D = dec.embed_size, dec.hidden_size
+        emb, w_lin, b_lin = dec.embedding.weight, dec.linear.weight, dec.linear.bias
+        V = w_lin.shape[0]
+        if feats.dim() != 2 or feats.size(1) != M:
+            raise ValueError(f"img_features must be (B, {M})")
+        self._begin(dev, B, V, max_steps, seed, uniforms, keep_logits, sync_every)
+        f = dict(device=dev, dtype=torch.float32)
+        scratch = None if STEP_FUSED else torch.empty(4, R, 4 * D, **f)
+        h0, c0 = torch.empty(B, D, **f), torch.empty(B, D, **f)
+        lstm_step(dec, B, h0, c0, x=feats, ld_x=M, scratch=scratch)
+        h = h0.repeat_interleave(n, 0).contiguous()
+        c = c0.repeat_interleave(n, 0).contiguous()
+        xin = torch.empty(R, M, **f)
+        h2, c2 = torch.empty(R, D, **f), torch.empty(R, D, **f)
+        prev = torch.full((R,), start_idx, dtype=torch.int64, device=dev)
+        for t_ in range(self.T):
+            K.embed_gather(emb, prev, R, 1, 1, xin, M)
+            lstm_step(dec, R, h2, c2, x=xin, ld_x=M, h_prev=h, c_prev=c, scratch=scratch)
+            logits = self._logits_at(t_)
+            K.gemm(K.problem(R, V, D, h2, D, w_lin, D, logits, V, bias=b_lin), AK, BW, K.TILE_64)
+            h, h2, c, c2 = h2, h, c2, c
+            if self._draw(logits, t_, V, end_idx, prev):
+                break
+        return self._finish(B, start_idx, end_idx)[0]

@@ -588,6 +588,28 @@ int capmi_beam_advance(const int* parent, const int* word, const float* top, int
                        float* fin_score, int* images_live, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Sampled decoding (csrc/sample.hip). New symbol only, nothing existing changed; added without an ABI bump
+ * (purely additive).
+ * ---------------------------------------------------------------------- */
+/* One decode step over R rows of fp32 logits (row r at logits + r*ld, ld >= V), one workgroup per row. A row with
+ * alive[r] == 0 is skipped: nothing of it is read or written. For an alive row, with l its logits:
+ *   kept set   0 < top_k < V: the top_k largest RAW logits, ties at the threshold to the lower index; otherwise all
+ *              of them. -inf logits are legal and carry weight 0.
+ *   temperature > 0: w_v = exp((l_v - l_max) / temperature) for kept v, else 0; S = sum w_v; token = the smallest
+ *              v with w_0 + ... + w_v > u[r] * S (u[r] in [0, 1); the inequality is strict, so a zero-weight entry
+ *              is never drawn and u = 0 gives the first kept entry with weight); when rounding leaves no such v
+ *              the last kept v with w_v > 0. logp = (l_tok - l_max) / temperature - log S.
+ *   temperature == 0: token = the smallest index attaining l_max; u and top_k are ignored; logp =
+ *              log_softmax(l)[token] (the step score beam search adds).
+ * Writes tokens[r], logp[r] (the caller passes row `step` of its (T, R) tables) and prev[r] = token; when token ==
+ * end_idx also alive[r] = 0 and *rows_live -= 1. All sums are fp32 in one fixed order: a row's result depends on
+ * its logits and u[r] alone. CAPMI_EINVAL on a NULL pointer, R < 1, V < 1, ld < V, step < 0, temperature < 0 or
+ * top_k < 0, CAPMI_ERANGE on V > 2^30, before any launch. */
+int capmi_sample_step(const float* logits, int ld, int R, int V, const float* u, float temperature, int top_k,
+                      int end_idx, int step, int* alive, long long* prev, int* tokens, float* logp,
+                      int* rows_live, void* stream);
+
+/* ------------------------------------------------------------------------
  * Teacher-forced validation (models/attention.py:454-567 for B captions at once; csrc/eval.hip).
  * Added under ABI 27: new symbols only, nothing existing changed.
  * ---------------------------------------------------------------------- */
