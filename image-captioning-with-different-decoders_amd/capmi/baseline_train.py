@@ -1,11 +1,11 @@
 """One 'baseline' (LSTM captioner) training step on the MI355X (reference models/baseline.py:114-264).
 
     x0 = embed(resnet(imgs))                       frozen ResNet-101 + the embed Linear
-    decoder forward                                embed_gather, hoisted (T B) x 4H x M GEMM with both biases,
+    decoder forward (capmi.baseline_core)          embed_gather, hoisted (T B) x 4H x M GEMM with both biases,
                                                    T x capmi_lstm_step_fwd_train, hoisted vocabulary GEMM
     loss = CrossEntropyLoss(ignore_index=PAD)      capmi_count_targets, capmi_ce_ignore_fwd_bwd (time-major
                                                    dlogits), capmi_loss_finalize_dev: the count stays on the device
-    backward                                       dH / dW_lin / db_lin, T x capmi_lstm_step_bwd, hoisted dW_ih,
+    backward (capmi.baseline_core)                 dH / dW_lin / db_lin, T x capmi_lstm_step_bwd, hoisted dW_ih,
                                                    dW_hh, bias column sums, dX, embedding scatter-add
     grads <- all-reduce mean over ranks            (DP only)
     params <- clamp(+-grad_clip) + Adam            capmi.optim.Adam: one kernel, step count on the device
@@ -32,11 +32,10 @@ import types
 
 import torch
 
+from . import baseline_core as core
 from . import dist as cdist
 from . import kernels as K
-from ._lib import CAPMI_A_KMAJOR, CAPMI_A_MMAJOR, CAPMI_B_KROWS, CAPMI_B_NMAJOR_W
-
-AK, AMM, BW, BKR = CAPMI_A_KMAJOR, CAPMI_A_MMAJOR, CAPMI_B_NMAJOR_W, CAPMI_B_KROWS
+from .baseline_core import AK, AMM, BKR, BW
 STEP_FUSED_FWD = True
 STEP_FUSED_BWD = True
 
@@ -101,86 +100,24 @@ class BaselineTrainStep:
         return feats
 
     def _forward(self, caps, ws):
-        dec = self.decoder
-        lstm, w_lin, b_lin = dec.lstm, dec.linear.weight, dec.linear.bias
-        w_ih, w_hh, b_ih, b_hh = lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0
-        B, L = caps.shape
-        T, M, Hd, V = L, dec.embed_size, dec.hidden_size, w_lin.shape[0]
-        sk = dec._capmi_ws(caps.device)
-        if T > 1:  # steps 1.. = embedding(captions[:, :-1])
-            K.embed_gather(dec.embedding.weight, caps, B, L, T - 1, ws.X[1:], M)
-        K.gemm_sk(K.problem(T * B, 4 * Hd, M, ws.X, M, w_ih, M, ws.GX, 4 * Hd, bias=b_ih, bias2=b_hh), AK, sk,
-                  K.TILE_AUTO)
-        for t in range(T):
-            pre = ws.GX[t * B:(t + 1) * B]
-            if self.fused_fwd:
-                if t == 0:
-                    K.lstm_step_fwd_train(B, M, Hd, ws.H[0], ws.C[0], ws.ACT[0], pre=pre)
-                else:
-                    K.lstm_step_fwd_train(B, M, Hd, ws.H[t], ws.C[t], ws.ACT[t], pre=pre, h_prev=ws.H[t - 1],
-                                          c_prev=ws.C[t - 1], w_hh=w_hh)
-                continue
-            if t > 0:
-                K.gemm(K.problem(B, 4 * Hd, Hd, ws.H[t - 1], Hd, w_hh, Hd, ws.HH, 4 * Hd), AK, BW, K.TILE_64)
-            K.lstm_cell_fwd(pre, 1, 0, None, ws.HH if t > 0 else None, 1 if t > 0 else 0, 0,
-                            ws.C[t - 1] if t > 0 else ws.zeros, B, Hd, ws.H[t], ws.C[t], ws.ACT[t])
-        # row r = t*B + b of the (T*B, V) product lands at logits[b][t]
-        K.gemm_sk(K.problem(T * B, V, Hd, ws.H, Hd, w_lin, Hd, ws.logits, T * V, c_r1=B, c_s2=V, bias=b_lin), AK, sk,
-                  K.TILE_AUTO)
-        K.count_targets(caps, B, T, L, 0, self.ignore_index, ws.count, ws.inv)
-        K.ce_ignore_fwd_bwd(ws.logits, caps, B, T, L, V, 0, self.ignore_index, ws.inv, ws.loss_rows, ws.dlogits, True)
+        B, T = caps.shape
+        core.forward(self.decoder, caps, ws.X, ws.GX, ws.H, ws.C, ws.logits, ws.ACT, fused=self.fused_fwd,
+                     scratch=(None, ws.HH, ws.zeros, None))
+        K.count_targets(caps, B, T, T, 0, self.ignore_index, ws.count, ws.inv)
+        K.ce_ignore_fwd_bwd(ws.logits, caps, B, T, T, ws.logits.shape[2], 0, self.ignore_index, ws.inv, ws.loss_rows,
+                            ws.dlogits, True)
         K.loss_finalize_dev(ws.loss_rows, B * T, ws.inv, ws.loss)
 
     def _backward(self, caps, ws, feats):
         dec = self.decoder
-        lstm, w_lin, b_lin, emb_w = dec.lstm, dec.linear.weight, dec.linear.bias, dec.embedding.weight
-        w_ih, w_hh, b_ih, b_hh = lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0
-        B, L = caps.shape
-        T, M, Hd, V = L, dec.embed_size, dec.hidden_size, w_lin.shape[0]
-        sk = dec._capmi_ws(caps.device)
-        dl = ws.dlogits  # (T*B, V), row t*B + b: the rows of H
-        K.gemm_sk(K.problem(T * B, Hd, V, dl, V, w_lin, Hd, ws.dH, Hd), AK, sk, K.TILE_AUTO, bmode=BKR)
-        if w_lin.requires_grad:  # dW_lin = dlogits^T H
-            K.gemm_sk(K.problem(V, Hd, T * B, dl, V, ws.H, Hd, w_lin.grad, Hd), AMM, sk, K.TILE_AUTO, bmode=BKR)
-        if b_lin.requires_grad:
-            K.colsum(dl, T * B, V, V, b_lin.grad, ws.cs_v)
-        for t in range(T - 1, -1, -1):
-            last = t == T - 1
-            dh_lin = ws.dH[t * B:(t + 1) * B]
-            dc_in = None if last else ws.DC[(t + 1) & 1]
-            if self.fused_bwd:
-                K.lstm_step_bwd(B, Hd, ws.ACT[t], ws.C[t], ws.DG[t], ws.DC[t & 1], dh_lin=dh_lin,
-                                dg_next=None if last else ws.DG[t + 1], w_hh=w_hh, dc_in=dc_in,
-                                c_prev=ws.C[t - 1] if t > 0 else None)
-                continue
-            if not last:  # dh_t (recurrent part) = dgates_{t+1} . W_hh
-                K.gemm(K.problem(B, Hd, 4 * Hd, ws.DG[t + 1], 4 * Hd, w_hh, Hd, ws.DHR, Hd), AK, BKR, K.TILE_64)
-            K.lstm_cell_bwd(dh_lin, ws.DHR, 0 if last else 1, 0, dc_in, ws.ACT[t], ws.C[t - 1] if t > 0 else ws.zeros,
-                            ws.C[t], B, Hd, B, ws.DG[t], ws.DC[t & 1])
-        if w_ih.requires_grad:  # dW_ih = DG^T X
-            K.gemm_sk(K.problem(4 * Hd, M, T * B, ws.DG, 4 * Hd, ws.X, M, w_ih.grad, M), AMM, sk, K.TILE_AUTO,
-                      bmode=BKR)
-        if w_hh.requires_grad:
-            if T > 1:  # dW_hh = sum_{t>=1} DG[t]^T H[t-1]
-                K.gemm_sk(K.problem(4 * Hd, Hd, (T - 1) * B, ws.DG[1:], 4 * Hd, ws.H, Hd, w_hh.grad, Hd), AMM, sk,
-                          K.TILE_AUTO, bmode=BKR)
-            else:
-                w_hh.grad.zero_()
-        if b_ih.requires_grad or b_hh.requires_grad:
-            K.colsum(ws.DG, T * B, 4 * Hd, 4 * Hd, ws.gb, ws.cs_g)
-            for b in (b_ih, b_hh):
-                if b.requires_grad:
-                    b.grad.copy_(ws.gb)
-        need_emb = emb_w.requires_grad and T > 1
-        if need_emb or self.train_embed:  # dX = DG . W_ih: step 0 -> the image feature, steps 1.. -> embedding rows
-            K.gemm_sk(K.problem(T * B, M, 4 * Hd, ws.DG, 4 * Hd, w_ih, M, ws.DX, M), AK, sk, K.TILE_AUTO, bmode=BKR)
-        if emb_w.requires_grad:
-            emb_w.grad.zero_()
-            if T > 1:
-                K.embed_scatter_add(ws.DX[1:], M, caps, B, L, T - 1, None, M, emb_w.grad)
+        grads = {n: q.grad for n, q in zip(core.PNAMES, core.params(dec)) if q.requires_grad}
+        # ws.dlogits is time-major (T*B, V), row t*B + b: the rows of H
+        core.backward(dec, caps, ws, ws.dlogits, grads, dlogits_time_major=True, fused=self.fused_bwd,
+                      need_dx=self.train_embed)
         if self.train_embed:
             emb = self.encoder.embed
-            F = feats.shape[1]
+            B, M, F = caps.shape[0], dec.embed_size, feats.shape[1]
+            sk = dec._capmi_ws(caps.device)
             if emb.weight.requires_grad:  # dW_embed = dX[0]^T feats
                 K.gemm_sk(K.problem(M, F, B, ws.DX[0], M, feats, F, emb.weight.grad, F), AMM, sk, K.TILE_AUTO,
                           bmode=BKR)

@@ -13,8 +13,8 @@ The reference project has no sampler; the semantics of a draw are stated at ``ca
 import torch
 
 from . import kernels as K
-from ._lib import CAPMI_A_KMAJOR as AK, CAPMI_B_NMAJOR_W as BW
-from .beam import BeamSearch
+from .baseline_core import check_inputs
+from .rollout import AttentionStepper, BaselineStepper
 
 KEEP_LOGITS_MAX_BYTES = 256 << 20
 
@@ -82,6 +82,18 @@ class _Rollout:
             return int(self.rows_live.item()) == 0
         return False
 
+    def _roll(self, st, start_idx, end_idx, step_args=lambda t_: ()):
+        """The rollout on stepper ``st``; ``step_args(t_)``: what its ``step`` takes beside the tokens and the
+        logits. Every row carries its own state on, so the stepper's two state pairs are swapped: nothing to
+        gather."""
+        prev = torch.full((st.R,), start_idx, dtype=torch.int64, device=st.dev)
+        for t_ in range(self.T):
+            logits = self._logits_at(t_)
+            st.step(prev, logits, *step_args(t_))
+            st.swap()
+            if self._draw(logits, t_, st.V, end_idx, prev):
+                break
+
     def _finish(self, B, start_idx, end_idx):
         """list of B lists of n dicts (without alphas), and per row the number of tokens it emitted"""
         T, R, n = self.T, self.R, self.n
@@ -124,8 +136,6 @@ class BatchedSampler(_Rollout):
         self.last_stats = None
         self.last_logits = None
 
-    _params = BeamSearch._params
-
     @torch.no_grad()
     def sample(self, encoder_out, start_idx, end_idx, max_steps=50, seed=None, uniforms=None, return_alphas=False,
                keep_logits=False, sync_every=8):
@@ -138,53 +148,14 @@ class BatchedSampler(_Rollout):
         the device. ``last_stats`` = steps run and host syncs taken."""
         if self.dec.use_bert:
             raise NotImplementedError("sampling with BERT features (as beam search)")
-        p = self._params()
-        dev = encoder_out.device
-        B, E = encoder_out.size(0), encoder_out.size(-1)
-        enc = encoder_out.reshape(B, -1, E).contiguous().float()
-        P, n = enc.size(1), self.n
-        R = B * n
-        A, D = p["W_ea"].shape[0], p["W_hh"].shape[1]
-        M, V = p["emb"].shape[1], p["W_fc"].shape[0]
-        X = M + E
-        self._begin(dev, B, V, max_steps, seed, uniforms, keep_logits, sync_every)
-        T = self.T
-        f = dict(device=dev, dtype=torch.float32)
-        # per batch: att_enc and the initial state, once per image
-        att_enc = torch.empty(B * P, A, **f)
-        K.gemm(K.problem(B * P, A, E, enc, E, p["W_ea"], E, att_enc, A, bias=p["b_ea"]), AK, BW, K.TILE_64)
-        mean = torch.empty(B, E, **f)
-        K.mean_rows(enc, B, P, E, mean)
-        h0, c0 = torch.empty(B, D, **f), torch.empty(B, D, **f)
-        K.gemm([K.problem(B, D, E, mean, E, p["W_h"], E, h0, D, bias=p["b_h"]),
-                K.problem(B, D, E, mean, E, p["W_c"], E, c0, D, bias=p["b_c"])], AK, BW, K.TILE_64)
-        h = h0.repeat_interleave(n, 0).contiguous()
-        c = c0.repeat_interleave(n, 0).contiguous()
-        xin = torch.zeros(R, X, **f)
-        p_ad, p_gate = torch.empty(R, A, **f), torch.empty(R, E, **f)
-        p_hh, p_x = torch.empty(R, 4 * D, **f), torch.empty(R, 4 * D, **f)
-        e_ws = torch.empty(R, P, **f)
-        act, h2, c2 = torch.empty(R, 4 * D, **f), torch.empty(R, D, **f), torch.empty(R, D, **f)
-        alphas = torch.zeros(T, R, P, **f) if return_alphas else None
+        dev, B, n = encoder_out.device, encoder_out.size(0), self.n
+        # the table's own checks come before the stepper's launches
+        self._begin(dev, B, self.dec.fc.weight.shape[0], max_steps, seed, uniforms, keep_logits, sync_every)
+        st = AttentionStepper(self.dec, encoder_out, n)
+        P = st.P
+        alphas = torch.zeros(self.T, st.R, P, device=dev, dtype=torch.float32) if return_alphas else None
         live = torch.full((B,), n, dtype=torch.int32, device=dev)
-        prev = torch.full((R,), start_idx, dtype=torch.int64, device=dev)
-
-        for t_ in range(T):
-            K.embed_gather(p["emb"], prev, R, 1, 1, xin, X)
-            K.gemm([K.problem(R, A, D, h, D, p["W_da"], D, p_ad, A),
-                    K.problem(R, E, D, h, D, p["W_fb"], D, p_gate, E),
-                    K.problem(R, 4 * D, D, h, D, p["W_hh"], D, p_hh, 4 * D)], AK, BW, K.TILE_64)
-            K.beam_att_fwd(enc, att_enc, p_ad, 1, 0, p["b_da"], p["wf"], p["bf"], p_gate, 1, 0, p["b_fb"], live,
-                           B, n, P, A, E, e_ws, alpha_out=alphas[t_] if return_alphas else None,
-                           x_out=xin[:, M:], ld_x=X)
-            K.gemm(K.problem(R, 4 * D, X, xin, X, p["W_ih"], X, p_x, 4 * D, bias=p["b_ih"], bias2=p["b_hh"]),
-                   AK, BW, K.TILE_64)
-            K.lstm_cell_fwd(p_x, 1, 0, None, p_hh, 1, 0, c, R, D, h2, c2, act)
-            logits = self._logits_at(t_)
-            K.gemm(K.problem(R, V, D, h2, D, p["W_fc"], D, logits, V, bias=p["b_fc"]), AK, BW, K.TILE_64)
-            h, h2, c, c2 = h2, h, c2, c  # every row carries its own state on: nothing to gather
-            if self._draw(logits, t_, V, end_idx, prev):
-                break
+        self._roll(st, start_idx, end_idx, lambda t_: (live, alphas[t_] if return_alphas else None))
         out, counts = self._finish(B, start_idx, end_idx)
         if return_alphas:
             al_h = alphas.cpu()
@@ -214,35 +185,10 @@ class BaselineBatchedSampler(_Rollout):
                sync_every=8):
         """img_features (B, M): the encoder's output. Returns what ``BatchedSampler.sample`` returns, every
         ``alphas`` empty."""
-        from .baseline_eval import STEP_FUSED, lstm_step
-        dec = self.dec
-        if not img_features.is_cuda:
-            raise RuntimeError("capmi baseline decoder path needs HIP tensors")
-        dev = img_features.device
-        feats = img_features.contiguous().float()
-        B, n = feats.size(0), self.n
-        R = B * n
-        M, D = dec.embed_size, dec.hidden_size
-        emb, w_lin, b_lin = dec.embedding.weight, dec.linear.weight, dec.linear.bias
-        V = w_lin.shape[0]
-        if feats.dim() != 2 or feats.size(1) != M:
-            raise ValueError(f"img_features must be (B, {M})")
-        self._begin(dev, B, V, max_steps, seed, uniforms, keep_logits, sync_every)
-        f = dict(device=dev, dtype=torch.float32)
-        scratch = None if STEP_FUSED else torch.empty(4, R, 4 * D, **f)
-        h0, c0 = torch.empty(B, D, **f), torch.empty(B, D, **f)
-        lstm_step(dec, B, h0, c0, x=feats, ld_x=M, scratch=scratch)
-        h = h0.repeat_interleave(n, 0).contiguous()
-        c = c0.repeat_interleave(n, 0).contiguous()
-        xin = torch.empty(R, M, **f)
-        h2, c2 = torch.empty(R, D, **f), torch.empty(R, D, **f)
-        prev = torch.full((R,), start_idx, dtype=torch.int64, device=dev)
-        for t_ in range(self.T):
-            K.embed_gather(emb, prev, R, 1, 1, xin, M)
-            lstm_step(dec, R, h2, c2, x=xin, ld_x=M, h_prev=h, c_prev=c, scratch=scratch)
-            logits = self._logits_at(t_)
-            K.gemm(K.problem(R, V, D, h2, D, w_lin, D, logits, V, bias=b_lin), AK, BW, K.TILE_64)
-            h, h2, c, c2 = h2, h, c2, c
-            if self._draw(logits, t_, V, end_idx, prev):
-                break
+        check_inputs(img_features)
+        B = img_features.size(0)
+        # the table's own checks come before the stepper's launch
+        self._begin(img_features.device, B, self.dec.linear.weight.shape[0], max_steps, seed, uniforms, keep_logits,
+                    sync_every)
+        self._roll(BaselineStepper(self.dec, img_features, self.n), start_idx, end_idx)
         return self._finish(B, start_idx, end_idx)[0]
