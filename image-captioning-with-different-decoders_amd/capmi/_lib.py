@@ -25,6 +25,7 @@ CAPMI_MAX_GROUP = 4
 CAPMI_COLSUM_GROUPS = 64
 ABI_VERSION = 27
 CAPMI_BNB_RELU_Y, CAPMI_BNB_RELU_OUT = 0, 1
+CAPMI_SCST_MEAN, CAPMI_SCST_GREEDY = 0, 1
 CAPMI_BNB_MAX_SLABS = 256
 CAPMI_GEMM_BF16 = 1
 CAPMI_GEMM_BF16_IO = 2
@@ -165,6 +166,12 @@ _SIGS = {
     "capmi_ce_ignore_fwd_bwd": [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_ll, c_vp, c_vp, c_vp, c_int,
                                 c_vp],
     "capmi_loss_finalize_dev": [c_vp, c_int, c_vp, c_vp, c_vp],
+    "capmi_rollout_pack": [c_vp, c_int, c_int, c_ll, c_int, c_ll, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "capmi_cider_reward": [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int,
+                           c_float, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "capmi_scst_advantage": [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp],
+    "capmi_pg_ce_fwd_bwd": [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp,
+                            c_vp, c_int, c_vp],
     "capmi_adam_clamp": [c_vp, c_vp, c_vp, c_vp, c_ll, c_double, c_double, c_double, c_double, c_double,
                          c_double, c_double, c_vp, c_vp],
     "capmi_adam_clamp_f64": [c_vp, c_vp, c_vp, c_vp, c_ll, c_double, c_double, c_double, c_double,

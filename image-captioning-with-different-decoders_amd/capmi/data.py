@@ -59,6 +59,20 @@ class SyntheticCOCO(torch.utils.data.Dataset):
         cap[-1] = self.V - 2
         return img, cap
 
+    def references(self, i, k=5):
+        """k seeded reference captions of image i (<start> words <end>, as an item's caption), the item's own
+        first: noisy copies of it (words kept, replaced or dropped), so they share n-grams as real references do."""
+        own = self[i][1]
+        g = torch.Generator().manual_seed(self.seed * 1000003 + i + 7919)
+        out = [own]
+        for _ in range(k - 1):
+            words = own[1:-1]
+            u = torch.rand(words.numel(), generator=g)
+            other = torch.randint(1, self.V - 3, (words.numel(),), generator=g)
+            words = torch.where(u < 0.2, other, words)[u < 0.9]
+            out.append(torch.cat([own[:1], words, own[-1:]]))
+        return out
+
 
 class SyntheticBertEmbedder:
     """Stand-in for the reference's BERT features (models/attention.py:166-215): bert-base-uncased

@@ -859,6 +859,60 @@ def loss_finalize_dev(loss_rows, n, inv_count, out):
     call("capmi_loss_finalize_dev", ptr(loss_rows), n, ptr(inv_count), ptr(out), stream())
 
 
+# --------------------------------------------------------------------------------------
+# self-critical training on sampled rollouts (csrc/scst.hip)
+# --------------------------------------------------------------------------------------
+def rollout_pack(tokens, T, R, start_idx, end_idx, pad_idx, lens, caps, count, inv_count):
+    """tokens (T, R) int32 (the sampler's table, -1 past a row's end) -> lens (R,), caps (R, T + 1) int64 =
+    [start, tokens.., pad..], count[0] = sum lens (optional) and inv_count[0] = 1 / count."""
+    _cuda(tokens, lens, count, dtype=torch.int32)
+    _cuda(caps, dtype=torch.int64)
+    _cuda(inv_count)
+    assert tokens.is_contiguous() and tokens.numel() >= T * R and lens.numel() >= R
+    assert caps.is_contiguous() and caps.numel() >= R * (T + 1)
+    call("capmi_rollout_pack", ptr(tokens), int(T), int(R), int(start_idx), int(end_idx), int(pad_idx), ptr(lens),
+         ptr(caps), ptr(count), ptr(inv_count), stream())
+
+
+def cider_reward(tokens, T, R, n, lens, img_key, refs, V, end_idx, score_end, reward):
+    """reward[r] = CIDEr-D of column r of tokens (T, R) against the references of image img_key[r // n] in
+    ``refs`` (capmi.scst.CiderRefs: the device tables). See capmi_cider_reward in capmi.h."""
+    _cuda(tokens, lens, img_key, refs.ref_off, refs.ref_bigrams, refs.img_off, dtype=torch.int32)
+    _cuda(refs.idf_keys, refs.ref_keys, dtype=torch.int64)  # the uint64 keys' bits
+    _cuda(refs.idf_vals, refs.ref_w, refs.ref_norm, reward)
+    assert tokens.is_contiguous() and tokens.numel() >= T * R and min(lens.numel(), reward.numel()) >= R
+    assert n >= 1 and R % n == 0 and img_key.numel() >= R // n
+    call("capmi_cider_reward", ptr(tokens), int(T), int(R), int(n), ptr(lens), ptr(img_key), int(refs.n_images),
+         int(V), int(end_idx), int(bool(score_end)), ptr(refs.idf_keys), ptr(refs.idf_vals), int(refs.n_keys),
+         float(refs.log_images), ptr(refs.ref_keys), ptr(refs.ref_w), ptr(refs.ref_off), ptr(refs.ref_norm),
+         ptr(refs.ref_bigrams), ptr(refs.img_off), ptr(reward), stream())
+
+
+def scst_advantage(reward, greedy_reward, B, n, mode, adv, stats):
+    """adv (B * n,) = reward minus the mean of the image's other samples (``mode`` CAPMI_SCST_MEAN, n >= 2) or
+    minus greedy_reward[b] (CAPMI_SCST_GREEDY); stats[0:2] = the mean reward and the mean greedy reward."""
+    _cuda(reward, greedy_reward, adv, stats)
+    assert min(reward.numel(), adv.numel()) >= B * n and stats.numel() >= 2
+    assert greedy_reward is None or greedy_reward.numel() >= B
+    call("capmi_scst_advantage", ptr(reward), ptr(greedy_reward), int(B), int(n), int(mode), ptr(adv), ptr(stats),
+         stream())
+
+
+def pg_ce_fwd_bwd(logits, caps, B, T, L, V, tgt_off, lens, t_first, adv, inv_count, logp_rows, loss_rows,
+                  dlogits=None, dl_time_major=False):
+    """ce_ignore_fwd_bwd weighted per caption: row (b, t) is live iff t_first <= t < t_first + lens[b]; it writes
+    logp_rows, loss_rows = -adv[b] logp and dlogits = adv[b] (softmax - onehot) inv_count[0]."""
+    _cuda(logits, adv, inv_count, logp_rows, loss_rows, dlogits)
+    _cuda(caps, dtype=torch.int64)
+    _cuda(lens, dtype=torch.int32)
+    assert logits.is_contiguous() and logits.numel() >= B * T * V
+    assert min(logp_rows.numel(), loss_rows.numel()) >= B * T and min(lens.numel(), adv.numel()) >= B
+    assert caps.is_contiguous() and caps.numel() >= B * L
+    assert dlogits is None or (dlogits.is_contiguous() and dlogits.numel() >= B * T * V)
+    call("capmi_pg_ce_fwd_bwd", ptr(logits), ptr(caps), B, T, L, V, int(tgt_off), ptr(lens), int(t_first), ptr(adv),
+         ptr(inv_count), ptr(logp_rows), ptr(loss_rows), ptr(dlogits), int(dl_time_major), stream())
+
+
 def ce_fwd_bwd(logits, caps, B, T, L, V, bt_dev, nrows, loss_rows, lse=None, dlogits=None,
                dl_time_major=False, gscale=None):
     _cuda(logits, loss_rows, lse, dlogits, gscale)

@@ -185,10 +185,21 @@ class BaselineBatchedSampler(_Rollout):
                sync_every=8):
         """img_features (B, M): the encoder's output. Returns what ``BatchedSampler.sample`` returns, every
         ``alphas`` empty."""
+        self.sample_device(img_features, start_idx, end_idx, max_steps, seed, uniforms, keep_logits, sync_every)
+        return self._finish(img_features.size(0), start_idx, end_idx)[0]
+
+    @torch.no_grad()
+    def sample_device(self, img_features, start_idx, end_idx, max_steps=50, seed=None, uniforms=None,
+                      keep_logits=False, sync_every=8):
+        """``sample`` without the copy to the host: the same launches, then the device views ``tokens`` (T, R)
+        int32 (-1 where a row had finished or the loop had stopped), ``logp`` (T, R), ``alive`` (R,) and the
+        number of steps run (T = max_steps + 1, R = B * num_samples). The views belong to this call: the next
+        one allocates its own."""
         check_inputs(img_features)
         B = img_features.size(0)
         # the table's own checks come before the stepper's launch
         self._begin(img_features.device, B, self.dec.linear.weight.shape[0], max_steps, seed, uniforms, keep_logits,
                     sync_every)
         self._roll(BaselineStepper(self.dec, img_features, self.n), start_idx, end_idx)
-        return self._finish(B, start_idx, end_idx)[0]
+        self.last_stats = {"steps": self.steps, "host_syncs": self.syncs}
+        return self.tokens, self.logp, self.alive, self.steps

@@ -67,6 +67,10 @@ class COCODataset(data.Dataset):
         return torch.LongTensor([self.vocab(START_TOKEN)] + [self.vocab(t) for t in tokens] +
                                 [self.vocab(END_TOKEN)])
 
+    def references(self, key):
+        """Every caption of the image with key `key` (its index in `img_ids`), numericalized as an item's."""
+        return [self._numericalize_caption(a['caption']) for a in self._get_annotations(self.img_ids[key])]
+
     def _img_path(self, img_id):
         return os.path.join(self.img_dir, self.coco.loadImgs(img_id)[0]['file_name'])
 

@@ -234,6 +234,161 @@ def _train_on_step(device, args, dataset, pad_idx, collate_fn):
               f'{time.time() - train_start:.4f} seconds.')
 
 
+class _KeyedItems(torch.utils.data.Dataset):
+    """(image, caption, key) items of a dataset whose items are (image, caption): the key is the item's index
+    (SyntheticCOCO: one image per item)."""
+
+    def __init__(self, dataset):
+        self.dataset, self.vocab = dataset, dataset.vocab
+
+    def __len__(self):
+        return len(self.dataset)
+
+    def __getitem__(self, i):
+        img, cap = self.dataset[i][:2]
+        return img, cap, i
+
+
+def check_self_critical_args(args):
+    """What ``--self_critical True`` asks of the other flags, before any data is loaded."""
+    if args.model != 'baseline':
+        raise NotImplementedError('--self_critical True: only --model baseline has a self-critical step '
+                                  '(the attention captioner needs its features repeated per sample)')
+    if not getattr(args, 'checkpoint', None):
+        raise SystemExit('--self_critical True continues from a cross-entropy trained model: give --checkpoint '
+                         '(a baseline state-dict checkpoint in ./checkpoints)')
+    if args.fine_tune_encoder:
+        raise NotImplementedError('--self_critical True with --fine_tune_encoder True: the features are computed '
+                                  'once per step, without a graph')
+    if not 0 <= args.sc_max_len <= 63:
+        raise SystemExit('--sc_max_len must be 0..63 (a sampled caption holds at most 64 words)')
+
+
+def train_self_critical(device, args):
+    """Self-critical training of a cross-entropy trained baseline captioner (capmi.scst): ``--checkpoint`` is
+    loaded as eval.py --model_type baseline loads it (sizes read off the tensors), the CIDEr-D tables are built
+    from the training set's captions grouped by image, and the loop of ``_train_on_step`` runs on
+    BaselineSelfCriticalStep over the distinct images of every batch. Loss, reward and (``--sc_baseline greedy``)
+    the greedy reward stay on the device and are read every ``print_freq`` batches and at the epoch's end."""
+    from capmi import dist as cdist
+    from capmi import kernels as K
+    from capmi.data import synthetic_requested
+    from capmi.imagepipe import ImageFeeder, collate_images, image_cache_for
+    from capmi.optim import Adam
+    from capmi.scst import MAX_REF_WORDS, BaselineSelfCriticalStep, CiderRefs
+    from checkpoint import load_checkpoint, unpack_checkpoint
+    from vocabulary import END_TOKEN, START_TOKEN
+    check_self_critical_args(args)
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("self-critical training runs on a HIP device (the rollouts and the reward are kernels)")
+    ctx = cdist.init_from_env(device)
+    device = ctx.device
+    if synthetic_requested(args):
+        from capmi.data import SyntheticCOCO
+        base = SyntheticCOCO.from_args(args)
+        dataset, n_images = _KeyedItems(base), len(base)
+    else:
+        from dataset import COCODataset  # real COCO path (needs pycocotools or capmi.coco, images)
+        dataset = base = COCODataset(mode='train', caption_max_len=args.max_caption_length, return_image_key=True)
+        n_images = len(base.img_ids)
+    vocab = dataset.vocab
+    pad_idx, start_idx, end_idx = vocab(PAD_TOKEN), vocab(START_TOKEN), vocab(END_TOKEN)
+    special = {pad_idx, start_idx, end_idx}
+    refs = CiderRefs.build([[[w for w in cap.tolist() if w not in special][:MAX_REF_WORDS] for cap in base.references(k)]
+                            for k in range(n_images)], end_idx=end_idx, device=device)
+    _, enc_sd, dec_sd, _, _, _ = unpack_checkpoint(
+        load_checkpoint(device, args, verbose=ctx.rank == 0, weights_only=not getattr(args, "trusted_checkpoint", False)))
+    if hasattr(dec_sd, 'state_dict'):  # a whole-module checkpoint
+        enc_sd, dec_sd = enc_sd.state_dict(), dec_sd.state_dict()
+    if len(vocab) != dec_sd["linear.weight"].shape[0]:
+        raise SystemError(f'checkpoint decodes {dec_sd["linear.weight"].shape[0]} words, the vocabulary has {len(vocab)}')
+    encoder = Encoder(enc_sd["embed.weight"].shape[0])
+    encoder.load_state_dict(enc_sd)
+    params = BaselineDecoderParams()
+    params.embed_size, params.hidden_size = dec_sd["embedding.weight"].shape[1], dec_sd["lstm.weight_hh_l0"].shape[1]
+    params.vocab_size = dec_sd["linear.weight"].shape[0]
+    decoder = BaselineDecoder(params)
+    if dec_sd["embedding.weight"].dtype == torch.float64:  # GloVe tables stay fp64
+        decoder.load_pretrained_embeddins(dec_sd["embedding.weight"].clone())
+    decoder.load_state_dict(dec_sd)
+    decoder.fine_tune_embeddings(on=args.fine_tune_embedding)
+    encoder, decoder = encoder.to(device), decoder.to(device)
+    cdist.broadcast_module(encoder, ctx)
+    cdist.broadcast_module(decoder, ctx)
+    for q in encoder.parameters():  # the features are inputs here
+        q.requires_grad = False
+    encoder.eval()
+    decoder.train()
+    cache = image_cache_for(args, base, device, args.batch_size)
+
+    def collate_fn(data):
+        seen, keep = set(), []
+        for item in data:  # an image appears once per step
+            if item[2] not in seen:
+                seen.add(item[2])
+                keep.append(item)
+        imgs, _, keys = zip(*keep)
+        return collate_images(imgs, keys if cache is not None else None), torch.tensor(keys, dtype=torch.int32)
+
+    sampler = cdist.sampler_for(dataset, ctx)
+    pin = not synthetic_requested(args)
+    loader = torch.utils.data.DataLoader(dataset, batch_size=args.batch_size, shuffle=sampler is None,
+                                         sampler=sampler, num_workers=args.workers, collate_fn=collate_fn,
+                                         pin_memory=pin, persistent_workers=args.workers > 0 and cache is not None)
+    feed = ImageFeeder(device, cache)
+    decoder_optimizer = Adam(filter(lambda p: p.requires_grad, decoder.parameters()), lr=args.decoder_lr)
+    step = BaselineSelfCriticalStep(encoder, decoder, decoder_optimizer, refs, ctx, num_samples=args.sc_samples,
+                                    temperature=args.sc_temperature, top_k=args.sc_top_k, baseline=args.sc_baseline,
+                                    max_steps=args.sc_max_len, score_end=True,
+                                    graph=os.environ.get("CAPMI_TRAIN_GRAPH", "1") != "0", start_idx=start_idx,
+                                    end_idx=end_idx, pad_idx=pad_idx)
+    train_self_critical.last_step = step  # (tests: which launch mode ran)
+    if pin and args.workers > 0:  # the loader's pin-memory thread allocates while a step is being captured
+        step.capture_error_mode = "thread_local"
+    greedy = args.sc_baseline == "greedy"
+    seed0 = int(torch.initial_seed()) % (1 << 31) + 7919 * ctx.rank
+    train_start = time.time()
+    num_batches = len(loader)
+    epoch_losses, epoch_rewards, it = [], [], 0
+    for epoch in range(args.epochs):
+        if sampler is not None:
+            sampler.set_epoch(epoch)
+        batch_losses, batch_rewards, pending = [], [], []
+        accum = [AccumulatingMetric(), AccumulatingMetric(), AccumulatingMetric()]
+        accum_time = AccumulatingMetric()
+        start = time.time()
+        for batch_idx, (imgs, keys) in enumerate(loader):
+            clip_gradient(decoder_optimizer, args.grad_clip)
+            loss = step(feed(imgs), keys, seed=seed0 + it)
+            it += 1
+            # the step's own buffers: the next call reuses them
+            pending.append(torch.cat([loss.detach(), step.last["reward_mean"],
+                                      step.last["greedy_reward_mean"] if greedy else loss.detach()]))
+            if batch_idx % args.print_freq == 0 or batch_idx == num_batches - 1:
+                torch.cuda.synchronize()
+                K.sk_check()
+                for l, r, g in torch.stack(pending).tolist():
+                    batch_losses.append(l)
+                    batch_rewards.append(r)
+                    for a, v in zip(accum, (l, r, g)):
+                        a.update(v)
+                pending = []
+                accum_time.update(time.time() - start)
+                if ctx.rank == 0 and batch_idx % args.print_freq == 0:
+                    print(f'Epoch {epoch+1}/{args.epochs}, Batch {batch_idx+1}/{num_batches}, '
+                          f'Loss {accum[0].avg():.4f}, Reward {accum[1].avg():.4f}, '
+                          + (f'Greedy {accum[2].avg():.4f}, ' if greedy else '') + f'Time: {accum_time.val:.4f}')
+            start = time.time()
+        epoch_losses.append(batch_losses)
+        epoch_rewards.append(batch_rewards)
+        if ctx.rank == 0:
+            save_checkpoint(args, epoch, encoder, decoder, None, decoder_optimizer,
+                            {'epoch_losses': epoch_losses, 'epoch_rewards': epoch_rewards})
+    if ctx.rank == 0:
+        print(f'Model {args.model_name} finished self-critical training for {args.epochs} epochs in '
+              f'{time.time() - train_start:.4f} seconds.')
+
+
 def _eval_dataset(args):
     """``args.dataset`` when the caller supplies one (items ``(img, caption)``, a ``vocab``), synthetic ragged
     captions for ``synthetic_size > 0``, else the reference's COCO 'val' set (needs the dataset)."""

@@ -5,8 +5,10 @@
 
 Flags, defaults and the argparse ``type=bool`` quirk (any non-empty string is True,
 Q10) are the reference's. Added: ``--synthetic`` (COCO-shaped synthetic data; the COCO
-pipeline is not part of this build), data parallelism from torchrun's env, and ``--image_cache_gb``
-(real COCO on the GPU: the resized uint8 images stay in device memory, each JPEG is decoded once per run).
+pipeline is not part of this build), data parallelism from torchrun's env, ``--image_cache_gb``
+(real COCO on the GPU: the resized uint8 images stay in device memory, each JPEG is decoded once per run), and
+``--self_critical True`` with its ``--sc_*`` flags (the baseline captioner continued from ``--checkpoint`` with a
+CIDEr-D policy gradient on sampled captions: models.baseline.train_self_critical).
 """
 import argparse
 import os
@@ -58,6 +60,15 @@ def parse_args(argv=None):
     parser.add_argument('--image_cache_gb', type=float, default=0,
                         help='GB of device memory for resized uint8 COCO images (150,528 B each; 12.5 GB holds '
                              'train2014): each JPEG is then decoded once per run. 0: off.')
+    parser.add_argument('--self_critical', type=bool, default=False,
+                        help='self-critical (CIDEr-D reward) training of --model baseline from --checkpoint.')
+    parser.add_argument('--sc_samples', type=int, default=5, help='sampled captions per image and step.')
+    parser.add_argument('--sc_baseline', type=str, default='mean', choices=['mean', 'greedy'],
+                        help="the advantage's baseline: the mean reward of the image's other samples, or the "
+                             "greedy caption's reward.")
+    parser.add_argument('--sc_temperature', type=float, default=1.0, help='sampling temperature.')
+    parser.add_argument('--sc_top_k', type=int, default=0, help='sample among the k likeliest words; 0: all.')
+    parser.add_argument('--sc_max_len', type=int, default=20, help='words of a sampled caption before END (<= 63).')
     return parser.parse_args(argv)
 
 
@@ -65,6 +76,9 @@ def main(argv=None):
     args = parse_args(argv)
     device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     from capmi.data import synthetic_requested
+    if args.self_critical:  # what the flag asks of the others comes before any data is looked for
+        from models.baseline import check_self_critical_args
+        check_self_critical_args(args)
     if not synthetic_requested(args) and not os.path.exists(PathConfig.vocab_file):
         raise SystemError('Must run "python init.py --vocab True" before training.')
     if args.use_glove:
@@ -74,6 +88,11 @@ def main(argv=None):
     if args.use_bert:
         assert args.model == 'attention', 'BERT is only used for attention model.'
         assert args.embed_size == 768, 'Expected embedding size of 768 for BERT.'
+    if args.self_critical:
+        from models.baseline import train_self_critical
+        print('Self-critical training of the baseline model...')
+        train_self_critical(device, args)
+        return
     if args.model == 'baseline':
         from models.baseline import train as train_baseline_model
         print('Training baseline model...')

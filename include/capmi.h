@@ -698,6 +698,58 @@ int capmi_ce_ignore_fwd_bwd(const float* logits, const long long* caps, int B, i
 int capmi_loss_finalize_dev(const float* loss_rows, int n, const float* inv_count, float* out, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Self-critical sequence training on sampled rollouts (csrc/scst.hip). New symbols only, nothing existing
+ * changed; added without an ABI bump (purely additive). Every reduction is fp32 in one fixed order, no float
+ * atomics; every argument is checked before any launch.
+ * ---------------------------------------------------------------------- */
+/* tokens (T, R) int32 as capmi_sample_step leaves its table: entry (t, r) is -1 where row r had finished or the
+ * loop had stopped. lens[r] = the number of leading entries >= 0 up to and including the first end_idx, in 0..T;
+ * caps (R, T + 1) int64 = [start_idx, tok_0 .. tok_{len-1}, pad_idx ..]; count[0] (may be NULL) = sum lens,
+ * inv_count[0] = 1 / count (count 0: +inf), on the device as capmi_count_targets keeps them. One workgroup.
+ * CAPMI_EINVAL on a NULL pointer (but count), T < 1, R < 1 or a negative index; CAPMI_ERANGE on R (T + 1) >= 2^31. */
+int capmi_rollout_pack(const int* tokens, int T, int R, long long start_idx, int end_idx, long long pad_idx,
+                       int* lens, long long* caps, int* count, float* inv_count, void* stream);
+/* reward[r] = the CIDEr-D of hypothesis row r (the first lens[r] entries of column r of tokens (T, R); score_end
+ * == 0 drops a final end_idx) against the references listed for image img_key[r / n] (reference
+ * eval_func/cider/cider_scorer.py for one hypothesis): n-gram orders 1..4, tf the raw count, idf = log_images -
+ * log(max(1, df)) from the corpus table, per order sum min(w_h, w_r) w_r / (|h| |r|) (the division skipped when
+ * either norm is 0), times exp(-(bigrams_h - bigrams_r)^2 / 72), mean over the orders and the listed references,
+ * times 10. An n-gram is a uint64 key: (token + 1) of its first word in bits 48..63, the next in 32..47, 16..31,
+ * 0..15, zero for the words a shorter n-gram lacks. Tables, built once by the host (capmi.scst.CiderRefs):
+ *   idf_keys / idf_vals [n_keys]  the corpus's distinct keys, ascending, and their fp32 idf; a key not found has
+ *                                 df 0: idf = log_images
+ *   ref_keys / ref_w              per reference its distinct keys ascending and w_r = tf * idf, entries
+ *                                 ref_off[j] .. ref_off[j + 1] - 1 of both
+ *   ref_norm [refs][4], ref_bigrams [refs]   the reference's norm per order and its number of bigrams
+ *   img_off [n_images + 1]        the references of image k are img_off[k] .. img_off[k + 1] - 1; one listed
+ *                                 twice is stored twice
+ * One workgroup per row; a row's reward depends on that row and the tables alone. img_key outside [0, n_images):
+ * reward NaN. CAPMI_EINVAL on a NULL pointer (the four entry tables may be NULL when n_keys == 0), T outside
+ * 1..64, R < 1, n < 1, R % n != 0, n_images < 1, V < 1, end_idx < 0 or a NaN log_images; CAPMI_ERANGE on
+ * V > 65534. */
+int capmi_cider_reward(const int* tokens, int T, int R, int n, const int* lens, const int* img_key, int n_images,
+                       int V, int end_idx, int score_end, const unsigned long long* idf_keys, const float* idf_vals,
+                       int n_keys, float log_images, const unsigned long long* ref_keys, const float* ref_w,
+                       const int* ref_off, const float* ref_norm, const int* ref_bigrams, const int* img_off,
+                       float* reward, void* stream);
+#define CAPMI_SCST_MEAN 0
+#define CAPMI_SCST_GREEDY 1
+/* reward (B, n). CAPMI_SCST_MEAN (n >= 2): adv[b n + j] = reward[b n + j] - mean_{k != j} reward[b n + k], the
+ * others added in index order. CAPMI_SCST_GREEDY: adv = reward - greedy_reward[b]. stats[0] = the mean of reward,
+ * stats[1] = the mean of greedy_reward (0 when NULL). One workgroup. */
+int capmi_scst_advantage(const float* reward, const float* greedy_reward, int B, int n, int mode, float* adv,
+                         float* stats, void* stream);
+/* capmi_ce_ignore_fwd_bwd weighted per caption: logits (B,T,V), rows r = b*T + t, target caps[b*L + t + tgt_off].
+ * Row (b, t) is live iff t_first <= t < t_first + lens[b] (and its target lies in [0, V)). A live row writes
+ * logp_rows[r] = x[target] - logsumexp(x), loss_rows[r] = -adv[b] logp and (dlogits non-NULL) adv[b] (softmax -
+ * onehot) inv_count[0]; any other row writes zeros to all three. dlogits row t*B + b when dl_time_major else
+ * b*T + t. The baseline decoder: tgt_off 0, t_first 1 (step 0 scores the image feature against START, which is
+ * no action); the attention decoder: tgt_off 1, t_first 0. capmi_loss_finalize_dev finishes the loss. */
+int capmi_pg_ce_fwd_bwd(const float* logits, const long long* caps, int B, int T, int L, int V, int tgt_off,
+                        const int* lens, int t_first, const float* adv, const float* inv_count, float* logp_rows,
+                        float* loss_rows, float* dlogits, int dl_time_major, void* stream);
+
+/* ------------------------------------------------------------------------
  * Optimiser (train_utils.py:2-12 clamp + torch.optim.Adam, models/attention.py:352-355,423-430)
  * p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps) with g clamped to +-clip first.
  * step_dev == NULL: bc1 = 1 - beta1^t and bc2_sqrt = sqrt(1 - beta2^t) as passed (host step t);
