@@ -172,6 +172,10 @@ _SIGS = {
     "capmi_scst_advantage": [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp],
     "capmi_pg_ce_fwd_bwd": [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp,
                             c_vp, c_int, c_vp],
+    "capmi_att_group_bwd": [c_vp, c_int, c_ll, c_vp, c_vp, c_vp, c_vp, c_ll, c_vp, c_vp, c_vp, c_int, c_int, c_int,
+                            c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "capmi_att_group_enc_grad": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,
+                                 ctypes.POINTER(c_int), c_vp],
     "capmi_adam_clamp": [c_vp, c_vp, c_vp, c_vp, c_ll, c_double, c_double, c_double, c_double, c_double,
                          c_double, c_double, c_vp, c_vp],
     "capmi_adam_clamp_f64": [c_vp, c_vp, c_vp, c_vp, c_ll, c_double, c_double, c_double, c_double,

@@ -992,6 +992,35 @@ def att_enc_grad_blocks(B, P):
 
 
 # --------------------------------------------------------------------------------------
+# attention backward over row groups sharing an image's features (csrc/att_group.hip): image i owns rows
+# i*n .. i*n+n-1, all live
+# --------------------------------------------------------------------------------------
+def att_group_bwd(dx_part, S, slab, gate, awe, enc, alpha, alpha_ld, att_enc, att_dec, wf, B, n, P, A, E, dalpha_ws,
+                  dgp, de, dad):
+    """One timestep of all R = B*n rows; enc (B, P, E) and att_enc (B, P, A) once per image."""
+    _cuda(dx_part, gate, awe, enc, alpha, att_enc, att_dec, wf, dalpha_ws, dgp, de, dad)
+    R = B * n
+    assert enc.is_contiguous() and att_enc.is_contiguous() and enc.numel() == B * P * E
+    assert att_enc.numel() == B * P * A and wf.numel() >= A and gate.numel() >= R * E and awe.numel() >= R * E
+    assert att_dec.numel() >= R * A and dalpha_ws.numel() >= R * P and dgp.numel() >= R * E
+    assert de.numel() >= R * P and dad.numel() >= R * A
+    call("capmi_att_group_bwd", ptr(dx_part), S, slab, ptr(gate), ptr(awe), ptr(enc), ptr(alpha), alpha_ld,
+         ptr(att_enc), ptr(att_dec), ptr(wf), B, n, P, A, E, ptr(dalpha_ws), ptr(dgp), ptr(de), ptr(dad), stream())
+
+
+def att_group_enc_grad(de, att_enc, att_dec, wf, T, B, n, P, A, datt_enc, wf_part, bf_part):
+    """de (T, B*n, P), att_dec (T, B*n, A); returns the number of wf_part / bf_part rows written."""
+    _cuda(de, att_enc, att_dec, wf, datt_enc, wf_part, bf_part)
+    nblk = att_enc_grad_blocks(B, P)
+    assert de.numel() >= T * B * n * P and att_dec.numel() >= T * B * n * A and att_enc.numel() == B * P * A
+    assert datt_enc.numel() >= B * P * A and wf_part.numel() >= nblk * A and bf_part.numel() >= nblk
+    k = ctypes.c_int(0)
+    call("capmi_att_group_enc_grad", ptr(de), ptr(att_enc), ptr(att_dec), ptr(wf), T, B, n, P, A, ptr(datt_enc),
+         ptr(wf_part), ptr(bf_part), ctypes.byref(k), stream())
+    return k.value
+
+
+# --------------------------------------------------------------------------------------
 # fused recurrence kernels (decoder_step.hip)
 # --------------------------------------------------------------------------------------
 def dstep_gemm(segs, M, N, nt, S, epi, part, counters, gate_D=0):

@@ -146,16 +146,9 @@ class BatchedSampler(_Rollout):
         S) or (emitted + 1, P) nested lists, a row of ones first, like beam search's; [] without
         ``return_alphas``). ``keep_logits``: every step's (R, V) logits stay in ``last_logits`` (T, R, V) on
         the device. ``last_stats`` = steps run and host syncs taken."""
-        if self.dec.use_bert:
-            raise NotImplementedError("sampling with BERT features (as beam search)")
-        dev, B, n = encoder_out.device, encoder_out.size(0), self.n
-        # the table's own checks come before the stepper's launches
-        self._begin(dev, B, self.dec.fc.weight.shape[0], max_steps, seed, uniforms, keep_logits, sync_every)
-        st = AttentionStepper(self.dec, encoder_out, n)
-        P = st.P
-        alphas = torch.zeros(self.T, st.R, P, device=dev, dtype=torch.float32) if return_alphas else None
-        live = torch.full((B,), n, dtype=torch.int32, device=dev)
-        self._roll(st, start_idx, end_idx, lambda t_: (live, alphas[t_] if return_alphas else None))
+        B, n = encoder_out.size(0), self.n
+        P, alphas = self._rollout(encoder_out, start_idx, end_idx, max_steps, seed, uniforms, keep_logits, sync_every,
+                                  return_alphas)
         out, counts = self._finish(B, start_idx, end_idx)
         if return_alphas:
             al_h = alphas.cpu()
@@ -166,6 +159,30 @@ class BatchedSampler(_Rollout):
                     al = al.view(-1, encoder_out.size(1), encoder_out.size(2))
                 out[r // n][r % n]["alphas"] = al.tolist()
         return out
+
+    def _rollout(self, encoder_out, start_idx, end_idx, max_steps, seed, uniforms, keep_logits, sync_every,
+                 return_alphas=False):
+        """The launches of one call; returns (P, the (T, R, P) alphas when wanted)."""
+        if self.dec.use_bert:
+            raise NotImplementedError("sampling with BERT features (as beam search)")
+        dev, B, n = encoder_out.device, encoder_out.size(0), self.n
+        # the table's own checks come before the stepper's launches
+        self._begin(dev, B, self.dec.fc.weight.shape[0], max_steps, seed, uniforms, keep_logits, sync_every)
+        st = AttentionStepper(self.dec, encoder_out, n)
+        alphas = torch.zeros(self.T, st.R, st.P, device=dev, dtype=torch.float32) if return_alphas else None
+        live = torch.full((B,), n, dtype=torch.int32, device=dev)
+        self._roll(st, start_idx, end_idx, lambda t_: (live, alphas[t_] if return_alphas else None))
+        return st.P, alphas
+
+    @torch.no_grad()
+    def sample_device(self, encoder_out, start_idx, end_idx, max_steps=50, seed=None, uniforms=None,
+                      keep_logits=False, sync_every=8):
+        """``sample`` without the copy to the host (and without alphas): the same launches, then the device views
+        ``tokens`` (T, R) int32 (-1 where a row had finished or the loop had stopped), ``logp`` (T, R), ``alive``
+        (R,) and the number of steps run, as ``BaselineBatchedSampler.sample_device`` returns them."""
+        self._rollout(encoder_out, start_idx, end_idx, max_steps, seed, uniforms, keep_logits, sync_every)
+        self.last_stats = {"steps": self.steps, "host_syncs": self.syncs}
+        return self.tokens, self.logp, self.alive, self.steps
 
 
 class BaselineBatchedSampler(_Rollout):

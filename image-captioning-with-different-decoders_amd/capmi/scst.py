@@ -1,14 +1,16 @@
-"""Self-critical sequence training (SCST) of the baseline (LSTM) captioner on the capmi kernels.
+"""Self-critical sequence training (SCST) of both captioners on the capmi kernels.
 
 The model samples ``n`` captions per image (capmi.sample), every caption is scored with CIDEr-D against the image's
 references on the device (``capmi_cider_reward`` on the sampler's own token table, no host copy), the reward minus
 a baseline (the mean of the image's other samples, or the greedy rollout's reward) weights the caption's
 log-probabilities, and one teacher-forced pass over the sampled captions gives the policy gradient
-(``capmi_pg_ce_fwd_bwd`` into ``baseline_core.backward``).
+(``capmi_pg_ce_fwd_bwd`` into ``baseline_core.backward``, or into capmi.decoder_group for the attention captioner,
+whose image features stay once per image through forward and backward).
 
 ``CiderRefs``          the device tables ``capmi_cider_reward`` reads, built once from the training captions
 ``cider_rewards_host`` the same per-hypothesis reward in fp64 Python, from the definitions (CPU fallback, oracle)
-``BaselineSelfCriticalStep``  rollout, reward, advantage, forward, weighted loss, backward, clamp + Adam
+``BaselineSelfCriticalStep`` / ``AttentionSelfCriticalStep``  rollout, reward, advantage, forward, weighted loss,
+                       backward, clamp + Adam
 
 The reference project has no self-critical training; its CIDEr scorer (eval_func/cider/cider_scorer.py) defines the
 reward, scored for one hypothesis at a time with the document frequencies of the whole reference corpus.
@@ -23,7 +25,9 @@ from . import baseline_core as core
 from . import kernels as K
 from ._lib import CAPMI_SCST_GREEDY, CAPMI_SCST_MEAN
 from .baseline_train import BaselineTrainStep
-from .sample import BaselineBatchedSampler
+from .decoder_core import PNAMES
+from .decoder_fn import decoder_params, gemm_flags
+from .sample import BaselineBatchedSampler, BatchedSampler
 from .scoring import CIDER_N, CIDER_SIGMA, _ngrams
 
 MAX_REF_WORDS = 63   # a reference and its END fill the 64 words a hypothesis may have
@@ -208,10 +212,15 @@ def hyps_from_table(tokens, lens):
     return [row[:int(k)] for row, k in zip(tok, lens.tolist())]
 
 
-class BaselineSelfCriticalStep(BaselineTrainStep):
-    """One self-critical step of the baseline captioner (module docstring). ``refs``: the ``CiderRefs`` of the
-    training captions, on the decoder's device. ``baseline``: "mean" (the mean reward of the image's other samples,
-    ``num_samples`` >= 2) or "greedy" (the reward of one temperature-0 rollout per image).
+class _SelfCriticalStep(BaselineTrainStep):
+    """What the self-critical steps of both captioners share: the rollouts, pack / reward / advantage, the launch
+    modes and ``last``. A subclass supplies its samplers (``_sampler``), the features of a batch (``_features``),
+    the decoder's buffers (``_decoder_buffers``) and the teacher-forced pass with the weighted loss and the
+    backward (``_policy_gradient``).
+
+    ``refs``: the ``CiderRefs`` of the training captions, on the decoder's device. ``baseline``: "mean" (the mean
+    reward of the image's other samples, ``num_samples`` >= 2) or "greedy" (the reward of one temperature-0 rollout
+    per image).
 
     ``graph=True`` captures everything after the rollouts (pack, reward, advantage, forward, weighted loss,
     backward, update) once per (B, n) into one linear HIP graph: the packed captions are always (B n, max_steps +
@@ -221,12 +230,8 @@ class BaselineSelfCriticalStep(BaselineTrainStep):
     same batch size: clone them to keep them. ``counts``: a capturing call counts as "capture", not as "replay".
     """
 
-    def __init__(self, encoder, decoder, optimizer, refs, ctx=None, num_samples=5, temperature=1.0, top_k=0,
-                 baseline="mean", max_steps=20, score_end=True, graph=False, start_idx=1, end_idx=2, pad_idx=0,
-                 encoder_optimizer=None):
-        if encoder_optimizer is not None:
-            raise NotImplementedError("self-critical training with a trainable embed Linear: the features are "
-                                      "computed once, without a graph")
+    def __init__(self, encoder, decoder, optimizer, refs, V, ctx=None, num_samples=5, temperature=1.0, top_k=0,
+                 baseline="mean", max_steps=20, score_end=True, graph=False, start_idx=1, end_idx=2, pad_idx=0):
         if baseline not in ("mean", "greedy"):
             raise ValueError('baseline must be "mean" or "greedy"')
         super().__init__(encoder, decoder, optimizer, ctx=ctx, graph=graph, ignore_index=pad_idx)
@@ -237,29 +242,34 @@ class BaselineSelfCriticalStep(BaselineTrainStep):
             raise ValueError(f"max_steps must be 0..{MAX_HYP_WORDS - 1} (a hypothesis of at most {MAX_HYP_WORDS} words)")
         self.refs, self.score_end = refs, bool(score_end)
         self.start_idx, self.end_idx, self.pad_idx = int(start_idx), int(end_idx), int(pad_idx)
-        self.V = decoder.linear.weight.shape[0]
+        self.V = int(V)
         if self.V > MAX_TOKEN + 1:
             raise ValueError(f"the vocabulary must not exceed {MAX_TOKEN + 1} words (16-bit n-gram fields)")
-        self.sampler = BaselineBatchedSampler(decoder, self.n, temperature, top_k)
-        self.greedy_sampler = BaselineBatchedSampler(decoder, 1, 0.0, 0) if baseline == "greedy" else None
+        self.sampler = self._sampler(self.n, temperature, top_k)
+        self.greedy_sampler = self._sampler(1, 0.0, 0) if baseline == "greedy" else None
         self.sync_every = 8
         self.last = None
         self._sc = {}
 
     # ------------------------------------------------------------------ buffers
-    def _sc_buffers(self, B):
+    def _sc_buffers(self, B, feats):
         sc = self._sc.get(B)
         if sc is not None:
+            if sc.feats.shape != feats.shape:
+                raise ValueError(f"the features of a batch of {B} were {tuple(sc.feats.shape)}, now "
+                                 f"{tuple(feats.shape)}: one feature shape per batch size")
             return sc
         n, T = self.n, self.max_steps + 1
-        R, dev = B * n, self.decoder.linear.weight.device
+        R, dev = B * n, feats.device
         i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)  # noqa: E731
         f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)  # noqa: E731
         sc = types.SimpleNamespace(
-            feats=f32(B, self.decoder.embed_size), img_key=i32(B), tokens=i32(T, R), lens=i32(R),
+            feats=torch.zeros_like(feats), img_key=i32(B), tokens=i32(T, R), lens=i32(R),
             caps=torch.zeros(R, T + 1, dtype=torch.int64, device=dev), reward=f32(R), adv=f32(R), stats=f32(2),
-            logp_rows=f32(R * (T + 1)), gtokens=i32(T, B), glens=i32(B), greward=f32(B),
-            gcaps=torch.zeros(B, T + 1, dtype=torch.int64, device=dev), ginv=f32(1), ws=self._buffers(R, T + 1))
+            gtokens=i32(T, B), glens=i32(B), greward=f32(B),
+            gcaps=torch.zeros(B, T + 1, dtype=torch.int64, device=dev), ginv=f32(1))
+        sc.ws, logp_cols = self._decoder_buffers(sc, B, R, T)
+        sc.logp_rows = f32(R * logp_cols)
         self._sc[B] = sc
         return sc
 
@@ -267,7 +277,7 @@ class BaselineSelfCriticalStep(BaselineTrainStep):
     def _grad_half(self, sc, B, own_reward, own_greedy, with_update):
         """Everything after the rollouts, on the static buffers of ``sc``: a linear chain of launches."""
         n, T, ws, refs = self.n, self.max_steps + 1, sc.ws, self.refs
-        R, L = B * n, T + 1
+        R = B * n
         K.rollout_pack(sc.tokens, T, R, self.start_idx, self.end_idx, self.pad_idx, sc.lens, sc.caps, ws.count, ws.inv)
         if own_reward:
             K.cider_reward(sc.tokens, T, R, n, sc.lens, sc.img_key, refs, self.V, self.end_idx, self.score_end,
@@ -280,15 +290,7 @@ class BaselineSelfCriticalStep(BaselineTrainStep):
                            sc.greward)
         K.scst_advantage(sc.reward, sc.greward if greedy else None, B, n,
                          CAPMI_SCST_GREEDY if greedy else CAPMI_SCST_MEAN, sc.adv, sc.stats)
-        # rows b n .. b n + n - 1 carry image b's feature, as in the sampler
-        ws.X[0].view(B, n, -1).copy_(sc.feats.unsqueeze(1).expand(B, n, sc.feats.size(1)))
-        core.forward(self.decoder, sc.caps, ws.X, ws.GX, ws.H, ws.C, ws.logits, ws.ACT, fused=self.fused_fwd,
-                     scratch=(None, ws.HH, ws.zeros, None))
-        # step 0 scores the image feature against START, which is no action: t_first = 1, target caps[t]
-        K.pg_ce_fwd_bwd(ws.logits, sc.caps, R, L, L, self.V, 0, sc.lens, 1, sc.adv, ws.inv, sc.logp_rows,
-                        ws.loss_rows, ws.dlogits, True)
-        K.loss_finalize_dev(ws.loss_rows, R * L, ws.inv, ws.loss)
-        self._backward(sc.caps, ws, None)
+        self._policy_gradient(sc, B)
         if with_update:
             self._step_all()
         return ws.loss
@@ -298,14 +300,15 @@ class BaselineSelfCriticalStep(BaselineTrainStep):
         the sampler's. ``rewards`` (B n,) / ``greedy_rewards`` (B,) replace the reward kernel's output (tests, other
         metrics). Returns the loss -sum adv logp / count (device tensor (1,), no host sync); ``last`` keeps
         reward_mean, greedy_reward_mean, lens, tokens, logp (the sampler's), adv, rewards, greedy_rewards, caps
-        (the packed captions) and logp_rows (R, max_steps + 2: the teacher-forced log-probabilities) as device
-        tensors. ``update=False`` (eager): gradients only, left in the optimizer's flat buffer."""
+        (the packed captions) and logp_rows (the teacher-forced log-probabilities, a row per caption: R, max_steps
+        + 2 for the baseline captioner, whose step 0 is the image; R, max_steps + 1 for the attention captioner)
+        as device tensors. ``update=False`` (eager): gradients only, left in the optimizer's flat buffer."""
         if not imgs.is_cuda:
-            raise RuntimeError("BaselineSelfCriticalStep needs HIP tensors")
+            raise RuntimeError(f"{type(self).__name__} needs HIP tensors")
         with torch.no_grad():
-            feats = self.encoder(imgs).float()
+            feats = self._features(imgs)
         B = feats.size(0)
-        sc = self._sc_buffers(B)
+        sc = self._sc_buffers(B, feats)
         sc.feats.copy_(feats)
         keys = torch.as_tensor(img_keys)
         if keys.numel() != B:
@@ -362,3 +365,102 @@ class BaselineSelfCriticalStep(BaselineTrainStep):
             self.counts["replay"] += 1
         g.replay()
         return sc.ws.loss
+
+
+class BaselineSelfCriticalStep(_SelfCriticalStep):
+    """One self-critical step of the baseline (LSTM) captioner (module docstring, ``_SelfCriticalStep``)."""
+
+    def __init__(self, encoder, decoder, optimizer, refs, ctx=None, num_samples=5, temperature=1.0, top_k=0,
+                 baseline="mean", max_steps=20, score_end=True, graph=False, start_idx=1, end_idx=2, pad_idx=0,
+                 encoder_optimizer=None):
+        if encoder_optimizer is not None:
+            raise NotImplementedError("self-critical training with a trainable embed Linear: the features are "
+                                      "computed once, without a graph")
+        super().__init__(encoder, decoder, optimizer, refs, decoder.linear.weight.shape[0], ctx, num_samples,
+                         temperature, top_k, baseline, max_steps, score_end, graph, start_idx, end_idx, pad_idx)
+
+    def _sampler(self, n, temperature, top_k):
+        return BaselineBatchedSampler(self.decoder, n, temperature, top_k)
+
+    def _features(self, imgs):
+        return self.encoder(imgs).float()
+
+    def _decoder_buffers(self, sc, B, R, T):
+        return self._buffers(R, T + 1), T + 1
+
+    def _policy_gradient(self, sc, B):
+        n, ws = self.n, sc.ws
+        R, L = B * n, self.max_steps + 2
+        # rows b n .. b n + n - 1 carry image b's feature, as in the sampler
+        ws.X[0].view(B, n, -1).copy_(sc.feats.unsqueeze(1).expand(B, n, sc.feats.size(1)))
+        core.forward(self.decoder, sc.caps, ws.X, ws.GX, ws.H, ws.C, ws.logits, ws.ACT, fused=self.fused_fwd,
+                     scratch=(None, ws.HH, ws.zeros, None))
+        # step 0 scores the image feature against START, which is no action: t_first = 1, target caps[t]
+        K.pg_ce_fwd_bwd(ws.logits, sc.caps, R, L, L, self.V, 0, sc.lens, 1, sc.adv, ws.inv, sc.logp_rows,
+                        ws.loss_rows, ws.dlogits, True)
+        K.loss_finalize_dev(ws.loss_rows, R * L, ws.inv, ws.loss)
+        self._backward(sc.caps, ws, None)
+
+
+class AttentionSelfCriticalStep(_SelfCriticalStep):
+    """One self-critical step of the soft-attention captioner (``_SelfCriticalStep``). The features (B, P, E),
+    whatever P the encoder gives, are computed once per image under ``no_grad`` and are never repeated per sample:
+    the rollouts run on ``capmi_beam_att_fwd`` (capmi.sample.BatchedSampler) and the teacher-forced pass over the
+    R = B n sampled captions on capmi.decoder_group (``capmi_att_group_bwd`` / ``capmi_att_group_enc_grad``
+    backward). Steps: features, rollouts (plus one greedy rollout per image for ``baseline="greedy"``), pack /
+    reward / advantage, grouped forward, ``capmi_pg_ce_fwd_bwd`` (target caps[t + 1], live steps 0 .. lens - 1,
+    time-major dlogits), ``capmi_loss_finalize_dev``, grouped backward, clamp + Adam.
+
+    The loss is -sum adv logp / count. There is no doubly-stochastic term (``alpha_c`` does not apply to sampled
+    captions with padded steps) and no dropout: the teacher-forced log-probabilities are the sampler's. The GEMMs
+    follow the decoder's ``compute_precision``. Not taken: a data-parallel context, a trainable encoder, BERT /
+    dense embeddings."""
+
+    def __init__(self, encoder, decoder, optimizer, refs, ctx=None, num_samples=5, temperature=1.0, top_k=0,
+                 baseline="mean", max_steps=20, score_end=True, graph=False, start_idx=1, end_idx=2, pad_idx=0):
+        from .decoder_group import N_MAX
+        if getattr(decoder, "use_bert", False):
+            raise NotImplementedError("self-critical training with BERT / dense word embeddings: the sampler has "
+                                      "no features for the tokens it draws")
+        if any(q.requires_grad for q in encoder.parameters()):
+            raise NotImplementedError("self-critical training with a trainable encoder: the features are computed "
+                                      "once per step, without a graph")
+        if ctx is not None and ctx.distributed:
+            raise NotImplementedError("data-parallel self-critical training of the attention captioner")
+        if int(num_samples) > N_MAX:
+            raise ValueError(f"num_samples must be <= {N_MAX} (the rows of an image one workgroup serves)")
+        super().__init__(encoder, decoder, optimizer, refs, decoder.fc.weight.shape[0], ctx, num_samples, temperature,
+                         top_k, baseline, max_steps, score_end, graph, start_idx, end_idx, pad_idx)
+        named = dict(decoder.named_parameters())
+        self.need = [k for k in PNAMES if named[k].requires_grad]
+        self._named = named
+
+    def _sampler(self, n, temperature, top_k):
+        return BatchedSampler(self.decoder, n, temperature, top_k)
+
+    def _features(self, imgs):
+        f = self.encoder(imgs).float()
+        return f.reshape(f.size(0), -1, f.size(-1)).contiguous()
+
+    def _decoder_buffers(self, sc, B, R, T):
+        from .decoder_group import GroupedDecoder
+        dev = sc.feats.device
+        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
+        sc.core = GroupedDecoder()  # one per batch size: a captured graph keeps its workspace
+        ws = types.SimpleNamespace(count=torch.zeros(1, dtype=torch.int32, device=dev), inv=f32(1), loss=f32(1),
+                                   loss_rows=f32(R * T), dlogits=f32(T * R, self.V))
+        return ws, T
+
+    def _policy_gradient(self, sc, B):
+        n, T, ws = self.n, self.max_steps + 1, sc.ws
+        R, L = B * n, T + 1
+        p = decoder_params(self.decoder)
+        preds, _, st = sc.core.forward(p, sc.feats, sc.caps, n, gemm_flags=gemm_flags(self.decoder))
+        # every step is an action: t_first = 0, target caps[t + 1]
+        K.pg_ce_fwd_bwd(preds, sc.caps, R, T, L, self.V, 1, sc.lens, 0, sc.adv, ws.inv, sc.logp_rows, ws.loss_rows,
+                        ws.dlogits, True)
+        K.loss_finalize_dev(ws.loss_rows, R * T, ws.inv, ws.loss)
+        grads = {k: self._named[k].grad for k in self.need}
+        if "attention.full_att.weight" in grads:
+            grads["attention.full_att.weight"] = grads["attention.full_att.weight"].view(-1)
+        sc.core.backward(p, st, grads, ws.dlogits, need=self.need)

@@ -316,6 +316,43 @@ def train(device, args):
         print(f'Model {args.model_name} finished training for {args.epochs} epochs.')
 
 
+def check_self_critical_args(args):
+    """What self-critical training of the attention captioner asks of the flags, before any data is loaded (the
+    twin of models.baseline.check_self_critical_args)."""
+    if not getattr(args, 'checkpoint', None):
+        raise SystemExit('self-critical training continues from a cross-entropy trained model: give --checkpoint '
+                         '(an attention state-dict checkpoint in ./checkpoints)')
+    if args.fine_tune_encoder:
+        raise NotImplementedError('self-critical training with --fine_tune_encoder True: the features are computed '
+                                  'once per step, without a graph')
+    if getattr(args, 'use_bert', False):
+        raise NotImplementedError('self-critical training with --use_bert True: the sampler has no BERT features '
+                                  'for the tokens it draws')
+    if not 0 <= args.sc_max_len <= 63:
+        raise SystemExit('--sc_max_len must be 0..63 (a sampled caption holds at most 64 words)')
+
+
+def train_self_critical(device, args):
+    """Self-critical training of a cross-entropy trained attention captioner (capmi.scst): the twin of
+    models.baseline.train_self_critical on the same ``--sc_*`` fields. ``args.checkpoint`` is loaded as eval.py
+    --model_type attention loads it (sizes read off the tensors), the CIDEr-D tables are built from the training
+    set's ``references(k)`` grouped by image, and AttentionSelfCriticalStep runs over the distinct images of every
+    batch. Loss, reward and (``sc_baseline`` greedy) the greedy reward stay on the device and are read every
+    ``print_freq`` batches and at the epoch's end. train.py does not dispatch here yet."""
+    from capmi.scst import AttentionSelfCriticalStep
+    from eval import _attention_models
+    from models.baseline import self_critical_data, self_critical_loop
+    check_self_critical_args(args)
+    ctx, device, base, dataset, refs = self_critical_data(device, args)
+    _, enc_sd, dec_sd, _, _, _ = unpack_checkpoint(
+        load_checkpoint(device, args, verbose=ctx.rank == 0, weights_only=not getattr(args, "trusted_checkpoint", False)))
+    if hasattr(dec_sd, 'state_dict'):  # a whole-module checkpoint
+        enc_sd, dec_sd = enc_sd.state_dict(), dec_sd.state_dict()
+    encoder, decoder = _attention_models(args, enc_sd, dec_sd, dataset.vocab, device)
+    self_critical_loop(args, ctx, device, base, dataset, refs, encoder, decoder, AttentionSelfCriticalStep,
+                       train_self_critical)
+
+
 def evaluate(device, args, encoder, decoder, val_loader=None):
     """Reference :454-567: one teacher-forced pass over the validation set (batch 1 in the
     reference), loss = CE over the packed rows + ((1 - sum_t alpha)^2).mean(), greedy argmax
@@ -460,4 +497,5 @@ def evaluate_batched(device, args, encoder, decoder, dataset=None, batch_size=64
     return metrics
 
 
-__all__ = ["SoftAttention", "AttentionDecoderParams", "AttentionDecoder", "train", "evaluate", "evaluate_batched"]
+__all__ = ["SoftAttention", "AttentionDecoderParams", "AttentionDecoder", "train", "train_self_critical", "evaluate",
+           "evaluate_batched"]

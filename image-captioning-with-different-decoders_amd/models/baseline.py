@@ -271,14 +271,40 @@ def train_self_critical(device, args):
     BaselineSelfCriticalStep over the distinct images of every batch. Loss, reward and (``--sc_baseline greedy``)
     the greedy reward stay on the device and are read every ``print_freq`` batches and at the epoch's end."""
     from capmi import dist as cdist
-    from capmi import kernels as K
-    from capmi.data import synthetic_requested
-    from capmi.imagepipe import ImageFeeder, collate_images, image_cache_for
-    from capmi.optim import Adam
-    from capmi.scst import MAX_REF_WORDS, BaselineSelfCriticalStep, CiderRefs
+    from capmi.scst import BaselineSelfCriticalStep
     from checkpoint import load_checkpoint, unpack_checkpoint
-    from vocabulary import END_TOKEN, START_TOKEN
     check_self_critical_args(args)
+    ctx, device, base, dataset, refs = self_critical_data(device, args)
+    _, enc_sd, dec_sd, _, _, _ = unpack_checkpoint(
+        load_checkpoint(device, args, verbose=ctx.rank == 0, weights_only=not getattr(args, "trusted_checkpoint", False)))
+    if hasattr(dec_sd, 'state_dict'):  # a whole-module checkpoint
+        enc_sd, dec_sd = enc_sd.state_dict(), dec_sd.state_dict()
+    if len(dataset.vocab) != dec_sd["linear.weight"].shape[0]:
+        raise SystemError(f'checkpoint decodes {dec_sd["linear.weight"].shape[0]} words, the vocabulary has '
+                          f'{len(dataset.vocab)}')
+    encoder = Encoder(enc_sd["embed.weight"].shape[0])
+    encoder.load_state_dict(enc_sd)
+    params = BaselineDecoderParams()
+    params.embed_size, params.hidden_size = dec_sd["embedding.weight"].shape[1], dec_sd["lstm.weight_hh_l0"].shape[1]
+    params.vocab_size = dec_sd["linear.weight"].shape[0]
+    decoder = BaselineDecoder(params)
+    if dec_sd["embedding.weight"].dtype == torch.float64:  # GloVe tables stay fp64
+        decoder.load_pretrained_embeddins(dec_sd["embedding.weight"].clone())
+    decoder.load_state_dict(dec_sd)
+    encoder, decoder = encoder.to(device), decoder.to(device)
+    cdist.broadcast_module(encoder, ctx)
+    cdist.broadcast_module(decoder, ctx)
+    self_critical_loop(args, ctx, device, base, dataset, refs, encoder, decoder, BaselineSelfCriticalStep,
+                       train_self_critical)
+
+
+def self_critical_data(device, args):
+    """The data side of self-critical training, for either captioner: (ctx, device, the training set, its (image,
+    caption, key) items, the ``CiderRefs`` of its captions grouped by image, END appended)."""
+    from capmi import dist as cdist
+    from capmi.data import synthetic_requested
+    from capmi.scst import MAX_REF_WORDS, CiderRefs
+    from vocabulary import END_TOKEN, START_TOKEN
     if torch.device(device).type != "cuda":
         raise RuntimeError("self-critical training runs on a HIP device (the rollouts and the reward are kernels)")
     ctx = cdist.init_from_env(device)
@@ -292,29 +318,25 @@ def train_self_critical(device, args):
         dataset = base = COCODataset(mode='train', caption_max_len=args.max_caption_length, return_image_key=True)
         n_images = len(base.img_ids)
     vocab = dataset.vocab
-    pad_idx, start_idx, end_idx = vocab(PAD_TOKEN), vocab(START_TOKEN), vocab(END_TOKEN)
-    special = {pad_idx, start_idx, end_idx}
+    end_idx = vocab(END_TOKEN)
+    special = {vocab(PAD_TOKEN), vocab(START_TOKEN), end_idx}
     refs = CiderRefs.build([[[w for w in cap.tolist() if w not in special][:MAX_REF_WORDS] for cap in base.references(k)]
                             for k in range(n_images)], end_idx=end_idx, device=device)
-    _, enc_sd, dec_sd, _, _, _ = unpack_checkpoint(
-        load_checkpoint(device, args, verbose=ctx.rank == 0, weights_only=not getattr(args, "trusted_checkpoint", False)))
-    if hasattr(dec_sd, 'state_dict'):  # a whole-module checkpoint
-        enc_sd, dec_sd = enc_sd.state_dict(), dec_sd.state_dict()
-    if len(vocab) != dec_sd["linear.weight"].shape[0]:
-        raise SystemError(f'checkpoint decodes {dec_sd["linear.weight"].shape[0]} words, the vocabulary has {len(vocab)}')
-    encoder = Encoder(enc_sd["embed.weight"].shape[0])
-    encoder.load_state_dict(enc_sd)
-    params = BaselineDecoderParams()
-    params.embed_size, params.hidden_size = dec_sd["embedding.weight"].shape[1], dec_sd["lstm.weight_hh_l0"].shape[1]
-    params.vocab_size = dec_sd["linear.weight"].shape[0]
-    decoder = BaselineDecoder(params)
-    if dec_sd["embedding.weight"].dtype == torch.float64:  # GloVe tables stay fp64
-        decoder.load_pretrained_embeddins(dec_sd["embedding.weight"].clone())
-    decoder.load_state_dict(dec_sd)
+    return ctx, device, base, dataset, refs
+
+
+def self_critical_loop(args, ctx, device, base, dataset, refs, encoder, decoder, step_class, owner):
+    """The training loop of self-critical training on ``step_class`` (capmi.scst) over the distinct images of
+    every batch; ``owner.last_step`` keeps the step (tests: which launch mode ran)."""
+    from capmi import dist as cdist
+    from capmi import kernels as K
+    from capmi.data import synthetic_requested
+    from capmi.imagepipe import ImageFeeder, collate_images, image_cache_for
+    from capmi.optim import Adam
+    from vocabulary import END_TOKEN, START_TOKEN
+    vocab = dataset.vocab
+    pad_idx, start_idx, end_idx = vocab(PAD_TOKEN), vocab(START_TOKEN), vocab(END_TOKEN)
     decoder.fine_tune_embeddings(on=args.fine_tune_embedding)
-    encoder, decoder = encoder.to(device), decoder.to(device)
-    cdist.broadcast_module(encoder, ctx)
-    cdist.broadcast_module(decoder, ctx)
     for q in encoder.parameters():  # the features are inputs here
         q.requires_grad = False
     encoder.eval()
@@ -337,12 +359,11 @@ def train_self_critical(device, args):
                                          pin_memory=pin, persistent_workers=args.workers > 0 and cache is not None)
     feed = ImageFeeder(device, cache)
     decoder_optimizer = Adam(filter(lambda p: p.requires_grad, decoder.parameters()), lr=args.decoder_lr)
-    step = BaselineSelfCriticalStep(encoder, decoder, decoder_optimizer, refs, ctx, num_samples=args.sc_samples,
-                                    temperature=args.sc_temperature, top_k=args.sc_top_k, baseline=args.sc_baseline,
-                                    max_steps=args.sc_max_len, score_end=True,
-                                    graph=os.environ.get("CAPMI_TRAIN_GRAPH", "1") != "0", start_idx=start_idx,
-                                    end_idx=end_idx, pad_idx=pad_idx)
-    train_self_critical.last_step = step  # (tests: which launch mode ran)
+    step = step_class(encoder, decoder, decoder_optimizer, refs, ctx, num_samples=args.sc_samples,
+                      temperature=args.sc_temperature, top_k=args.sc_top_k, baseline=args.sc_baseline,
+                      max_steps=args.sc_max_len, score_end=True, graph=os.environ.get("CAPMI_TRAIN_GRAPH", "1") != "0",
+                      start_idx=start_idx, end_idx=end_idx, pad_idx=pad_idx)
+    owner.last_step = step
     if pin and args.workers > 0:  # the loader's pin-memory thread allocates while a step is being captured
         step.capture_error_mode = "thread_local"
     greedy = args.sc_baseline == "greedy"

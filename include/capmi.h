@@ -750,6 +750,37 @@ int capmi_pg_ce_fwd_bwd(const float* logits, const long long* caps, int B, int T
                         float* loss_rows, float* dlogits, int dl_time_major, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Attention backward over row groups that share one image's features (csrc/att_group.hip): the teacher-forced
+ * pass over the R = B*n sampled captions of self-critical training, the backward of capmi_beam_att_fwd. Row layout
+ * as there: image i owns rows i*n .. i*n+n-1, 1 <= n <= 16; every row is live. enc [B][P][E] and att_enc [B][P][A]
+ * are stored once per image and each element a workgroup needs is loaded once for all n rows. New symbols only,
+ * added without an ABI bump (purely additive). Every sum has one fixed order that depends neither on n nor on the
+ * row's place in its group; no float atomics; every argument is checked before any launch.
+ * ---------------------------------------------------------------------- */
+/* One timestep, all R rows: capmi_att_ctx_bwd followed by capmi_att_score_bwd without dreg and bt.
+ *   d = sum of the S slabs dx_part[s*slab + r*E + e] (d(gate*awe));  dgp[r][e] = d awe gate (1 - gate)
+ *   dalpha[r][p] = (d gate)[r] . enc[r/n][p][:]   (dalpha_ws, [R][P] scratch)
+ *   de[r][p] = alpha (dalpha - sum_p alpha dalpha), alpha read at alpha[r*alpha_ld + p]
+ *   dad[r][a] = wf[a] sum_p de[r][p] [att_enc[r/n][p][a] + att_dec[r][a] > 0]
+ * gate, awe, dgp [R][E]; att_dec, dad [R][A]; de [R][P]. Two launches. CAPMI_EINVAL on a NULL pointer, B, P, A, E
+ * < 1, S < 1, n outside 1..16 or alpha_ld < P; CAPMI_ERANGE on A % 4, E % 4 or slab % 4 != 0, B > 65535, n*E*4 >
+ * 144 KiB or n*P*4 > 48 KiB (the rows' d(awe) / de are held in LDS); CAPMI_EALIGN on a pointer off 16 bytes. */
+int capmi_att_group_bwd(const float* dx_part, int S, long long slab, const float* gate, const float* awe,
+                        const float* enc, const float* alpha, long long alpha_ld, const float* att_enc,
+                        const float* att_dec, const float* wf, int B, int n, int P, int A, int E, float* dalpha_ws,
+                        float* dgp, float* de, float* dad, void* stream);
+/* Hoisted over all t and the n rows of an image, de [T][R][P], att_dec [T][R][A], R = B*n:
+ *   datt_enc[i][p][a] = wf[a] sum_t sum_{j<n} de[t][i*n+j][p] [att_enc[i][p][a] + att_dec[t][i*n+j][a] > 0]
+ * summed t ascending, then j ascending; wf_part[blk][a] = sum de*relu(.), bf_part[blk] = sum de over the block's
+ * slots (blk = one per (i, 28-slot chunk), *nblk_out of them; capmi_colsum reduces them). The T*n att_dec rows of
+ * a group are staged through LDS in chunks of (t, j) pairs (<= 55 KiB whatever T and n). CAPMI_EINVAL on a NULL
+ * pointer (but nblk_out), T, B, P, A < 1 or n outside 1..16; CAPMI_ERANGE on A % 4 != 0, A / 4 > 256, B or T >
+ * 65535; CAPMI_EALIGN on a pointer off 16 bytes. */
+int capmi_att_group_enc_grad(const float* de, const float* att_enc, const float* att_dec, const float* wf, int T,
+                             int B, int n, int P, int A, float* datt_enc, float* wf_part, float* bf_part,
+                             int* nblk_out, void* stream);
+
+/* ------------------------------------------------------------------------
  * Optimiser (train_utils.py:2-12 clamp + torch.optim.Adam, models/attention.py:352-355,423-430)
  * p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps) with g clamped to +-clip first.
  * step_dev == NULL: bc1 = 1 - beta1^t and bc2_sqrt = sqrt(1 - beta2^t) as passed (host step t);
