@@ -26,6 +26,7 @@ CAPMI_COLSUM_GROUPS = 64
 ABI_VERSION = 27
 CAPMI_BNB_RELU_Y, CAPMI_BNB_RELU_OUT = 0, 1
 CAPMI_SCST_MEAN, CAPMI_SCST_GREEDY = 0, 1
+CAPMI_SCORE_STATS = 14
 CAPMI_BNB_MAX_SLABS = 256
 CAPMI_GEMM_BF16 = 1
 CAPMI_GEMM_BF16_IO = 2
@@ -172,6 +173,9 @@ _SIGS = {
     "capmi_scst_advantage": [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp],
     "capmi_pg_ce_fwd_bwd": [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp,
                             c_vp, c_int, c_vp],
+    "capmi_caption_stats": [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int,
+                            c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "capmi_reward_mix": [c_vp, c_vp, c_ll, c_vp, c_int, c_double, c_double, c_double, c_vp, c_vp],
     "capmi_att_group_bwd": [c_vp, c_int, c_ll, c_vp, c_vp, c_vp, c_vp, c_ll, c_vp, c_vp, c_vp, c_int, c_int, c_int,
                             c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
     "capmi_att_group_enc_grad": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,

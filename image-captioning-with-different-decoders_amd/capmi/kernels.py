@@ -913,6 +913,38 @@ def pg_ce_fwd_bwd(logits, caps, B, T, L, V, tgt_off, lens, t_first, adv, inv_cou
          ptr(inv_count), ptr(logp_rows), ptr(loss_rows), ptr(dlogits), int(dl_time_major), stream())
 
 
+# --------------------------------------------------------------------------------------
+# caption metrics on the token table (csrc/score.hip)
+# --------------------------------------------------------------------------------------
+def caption_stats(tokens, T, R, n, lens, img_key, refs, V, end_idx, score_end, stats, bleu, rouge):
+    """Per column r of tokens (T, R): stats[r] (CAPMI_SCORE_STATS int32: BLEU matches / guesses / lengths, the
+    ROUGE-L LCS integers), bleu[r] (4,) and rouge[r], sentence-level, against the references of image
+    img_key[r // n] in ``refs`` (capmi.devscore.ScoreRefs). See capmi_caption_stats in capmi.h."""
+    from ._lib import CAPMI_SCORE_STATS
+    _cuda(tokens, lens, img_key, refs.bleu_cnt, refs.bleu_off, refs.ref_tok, refs.ref_off, refs.ref_len,
+          refs.rimg_off, stats, dtype=torch.int32)
+    _cuda(refs.bleu_keys, dtype=torch.int64)  # the uint64 keys' bits
+    _cuda(bleu, rouge)
+    assert tokens.is_contiguous() and tokens.numel() >= T * R and min(lens.numel(), rouge.numel()) >= R
+    assert stats.is_contiguous() and stats.numel() >= R * CAPMI_SCORE_STATS
+    assert bleu.is_contiguous() and bleu.numel() >= R * 4
+    assert n >= 1 and R % n == 0 and img_key.numel() >= R // n
+    call("capmi_caption_stats", ptr(tokens), int(T), int(R), int(n), ptr(lens), ptr(img_key), int(refs.n_images),
+         int(V), int(end_idx), int(bool(score_end)), ptr(refs.bleu_keys), ptr(refs.bleu_cnt), int(refs.n_keys),
+         ptr(refs.bleu_off), ptr(refs.ref_tok), int(refs.n_tok), ptr(refs.ref_off), ptr(refs.ref_len),
+         ptr(refs.rimg_off), ptr(stats), ptr(bleu), ptr(rouge), stream())
+
+
+def reward_mix(cider, bleu, rouge, R, w_cider, w_bleu4, w_rouge, reward):
+    """reward (R,) = w_cider cider + w_bleu4 bleu[:, 3] + w_rouge rouge in fp64, rounded once; ``bleu`` is
+    capmi_caption_stats's (R, 4)."""
+    _cuda(cider, bleu, rouge, reward)
+    assert bleu.is_contiguous() and bleu.numel() >= R * 4
+    assert min(cider.numel(), rouge.numel(), reward.numel()) >= R
+    call("capmi_reward_mix", ptr(cider), bleu.data_ptr() + 3 * 4, 4, ptr(rouge), int(R), float(w_cider),
+         float(w_bleu4), float(w_rouge), ptr(reward), stream())
+
+
 def ce_fwd_bwd(logits, caps, B, T, L, V, bt_dev, nrows, loss_rows, lse=None, dlogits=None,
                dl_time_major=False, gscale=None):
     _cuda(logits, loss_rows, lse, dlogits, gscale)

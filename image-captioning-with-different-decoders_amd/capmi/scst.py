@@ -9,6 +9,8 @@ whose image features stay once per image through forward and backward).
 
 ``CiderRefs``          the device tables ``capmi_cider_reward`` reads, built once from the training captions
 ``cider_rewards_host`` the same per-hypothesis reward in fp64 Python, from the definitions (CPU fallback, oracle)
+``reward_mix``         of both steps: train on a weighted sum of CIDEr-D, BLEU-4 and ROUGE-L instead (the tables and
+                       kernels of capmi.devscore, csrc/score.hip)
 ``BaselineSelfCriticalStep`` / ``AttentionSelfCriticalStep``  rollout, reward, advantage, forward, weighted loss,
                        backward, clamp + Adam
 
@@ -222,6 +224,11 @@ class _SelfCriticalStep(BaselineTrainStep):
     reward of the image's other samples, ``num_samples`` >= 2) or "greedy" (the reward of one temperature-0 rollout
     per image).
 
+    ``reward_mix``: None (CIDEr-D alone) or weights such as ``dict(cider=1.0, bleu4=0.5, rouge_l=0.0)``: the reward
+    is their weighted sum of CIDEr-D, sentence-level BLEU-4 and ROUGE-L (``capmi_caption_stats``,
+    ``capmi_reward_mix``; the greedy rollout's likewise), ``refs`` must then be a ``capmi.devscore.ScoreRefs`` and
+    ``last`` also keeps ``cider``, ``bleu4`` and ``rouge_l`` per sampled row.
+
     ``graph=True`` captures everything after the rollouts (pack, reward, advantage, forward, weighted loss,
     backward, update) once per (B, n) into one linear HIP graph: the packed captions are always (B n, max_steps +
     2). The rollouts stay eager: they stop early on a host read.
@@ -231,7 +238,8 @@ class _SelfCriticalStep(BaselineTrainStep):
     """
 
     def __init__(self, encoder, decoder, optimizer, refs, V, ctx=None, num_samples=5, temperature=1.0, top_k=0,
-                 baseline="mean", max_steps=20, score_end=True, graph=False, start_idx=1, end_idx=2, pad_idx=0):
+                 baseline="mean", max_steps=20, score_end=True, graph=False, start_idx=1, end_idx=2, pad_idx=0,
+                 reward_mix=None):
         if baseline not in ("mean", "greedy"):
             raise ValueError('baseline must be "mean" or "greedy"')
         super().__init__(encoder, decoder, optimizer, ctx=ctx, graph=graph, ignore_index=pad_idx)
@@ -241,6 +249,8 @@ class _SelfCriticalStep(BaselineTrainStep):
         if not 1 <= self.max_steps + 1 <= MAX_HYP_WORDS:
             raise ValueError(f"max_steps must be 0..{MAX_HYP_WORDS - 1} (a hypothesis of at most {MAX_HYP_WORDS} words)")
         self.refs, self.score_end = refs, bool(score_end)
+        self.reward_mix = self._check_mix(reward_mix, refs)
+        self._cider_refs = refs if self.reward_mix is None else refs.cider
         self.start_idx, self.end_idx, self.pad_idx = int(start_idx), int(end_idx), int(pad_idx)
         self.V = int(V)
         if self.V > MAX_TOKEN + 1:
@@ -250,6 +260,21 @@ class _SelfCriticalStep(BaselineTrainStep):
         self.sync_every = 8
         self.last = None
         self._sc = {}
+
+    @staticmethod
+    def _check_mix(reward_mix, refs):
+        """The weights (cider, bleu4, rouge_l) of a mixed reward, or None."""
+        if reward_mix is None:
+            return None
+        from .devscore import METRICS, ScoreRefs
+        if not isinstance(reward_mix, dict) or not reward_mix or set(reward_mix) - set(METRICS):
+            raise ValueError(f"reward_mix must be a dict of weights over {METRICS}")
+        weights = tuple(float(reward_mix.get(k, 0.0)) for k in METRICS)
+        if not all(math.isfinite(w) for w in weights):
+            raise ValueError("reward_mix weights must be finite")
+        if not isinstance(refs, ScoreRefs):
+            raise ValueError("reward_mix needs refs to be a capmi.devscore.ScoreRefs (BLEU and ROUGE-L tables)")
+        return weights
 
     # ------------------------------------------------------------------ buffers
     def _sc_buffers(self, B, feats):
@@ -268,6 +293,13 @@ class _SelfCriticalStep(BaselineTrainStep):
             caps=torch.zeros(R, T + 1, dtype=torch.int64, device=dev), reward=f32(R), adv=f32(R), stats=f32(2),
             gtokens=i32(T, B), glens=i32(B), greward=f32(B),
             gcaps=torch.zeros(B, T + 1, dtype=torch.int64, device=dev), ginv=f32(1))
+        if self.reward_mix is not None:  # the three components of the sampled and the greedy rows
+            from ._lib import CAPMI_SCORE_STATS
+            for name, rows in (("", R), ("g", B)):
+                setattr(sc, name + "cider", f32(rows))
+                setattr(sc, name + "bleu", f32(rows, 4))
+                setattr(sc, name + "rouge", f32(rows))
+                setattr(sc, name + "score_stats", i32(rows, CAPMI_SCORE_STATS))
         sc.ws, logp_cols = self._decoder_buffers(sc, B, R, T)
         sc.logp_rows = f32(R * logp_cols)
         self._sc[B] = sc
@@ -276,24 +308,35 @@ class _SelfCriticalStep(BaselineTrainStep):
     # ------------------------------------------------------------------ the step
     def _grad_half(self, sc, B, own_reward, own_greedy, with_update):
         """Everything after the rollouts, on the static buffers of ``sc``: a linear chain of launches."""
-        n, T, ws, refs = self.n, self.max_steps + 1, sc.ws, self.refs
+        n, T, ws = self.n, self.max_steps + 1, sc.ws
         R = B * n
         K.rollout_pack(sc.tokens, T, R, self.start_idx, self.end_idx, self.pad_idx, sc.lens, sc.caps, ws.count, ws.inv)
         if own_reward:
-            K.cider_reward(sc.tokens, T, R, n, sc.lens, sc.img_key, refs, self.V, self.end_idx, self.score_end,
-                           sc.reward)
+            self._reward(sc, sc.tokens, T, R, n, sc.lens, "", sc.reward)
         greedy = self.baseline == "greedy"
         if greedy and own_greedy:
             K.rollout_pack(sc.gtokens, T, B, self.start_idx, self.end_idx, self.pad_idx, sc.glens, sc.gcaps, None,
                            sc.ginv)
-            K.cider_reward(sc.gtokens, T, B, 1, sc.glens, sc.img_key, refs, self.V, self.end_idx, self.score_end,
-                           sc.greward)
+            self._reward(sc, sc.gtokens, T, B, 1, sc.glens, "g", sc.greward)
         K.scst_advantage(sc.reward, sc.greward if greedy else None, B, n,
                          CAPMI_SCST_GREEDY if greedy else CAPMI_SCST_MEAN, sc.adv, sc.stats)
         self._policy_gradient(sc, B)
         if with_update:
             self._step_all()
         return ws.loss
+
+    def _reward(self, sc, tokens, T, R, n, lens, which, reward):
+        """CIDEr-D into ``reward``; with a ``reward_mix`` the three metrics into the ``which`` ("" sampled, "g"
+        greedy) component buffers and their weighted sum into ``reward``."""
+        if self.reward_mix is None:
+            K.cider_reward(tokens, T, R, n, lens, sc.img_key, self._cider_refs, self.V, self.end_idx, self.score_end,
+                           reward)
+            return
+        cider, bleu, rouge = (getattr(sc, which + k) for k in ("cider", "bleu", "rouge"))
+        K.cider_reward(tokens, T, R, n, lens, sc.img_key, self._cider_refs, self.V, self.end_idx, self.score_end, cider)
+        K.caption_stats(tokens, T, R, n, lens, sc.img_key, self.refs, self.V, self.end_idx, self.score_end,
+                        getattr(sc, which + "score_stats"), bleu, rouge)
+        K.reward_mix(cider, bleu, rouge, R, *self.reward_mix, reward)
 
     def __call__(self, imgs, img_keys, seed=None, uniforms=None, rewards=None, greedy_rewards=None, update=True):
         """imgs: what the encoder takes, B images; img_keys (B,): their keys in ``refs``. ``seed`` / ``uniforms``:
@@ -339,6 +382,8 @@ class _SelfCriticalStep(BaselineTrainStep):
                          lens=sc.lens, tokens=sc.tokens, logp=logp, adv=sc.adv, rewards=sc.reward,
                          greedy_rewards=sc.greward if greedy else None, caps=sc.caps,
                          logp_rows=sc.logp_rows.view(B * self.n, -1))
+        if self.reward_mix is not None:  # the components of the kernels' own rewards (stale under ``rewards=``)
+            self.last.update(cider=sc.cider, bleu4=sc.bleu[:, 3], rouge_l=sc.rouge)
         return loss
 
     # ------------------------------------------------------------------ graph
@@ -372,12 +417,13 @@ class BaselineSelfCriticalStep(_SelfCriticalStep):
 
     def __init__(self, encoder, decoder, optimizer, refs, ctx=None, num_samples=5, temperature=1.0, top_k=0,
                  baseline="mean", max_steps=20, score_end=True, graph=False, start_idx=1, end_idx=2, pad_idx=0,
-                 encoder_optimizer=None):
+                 encoder_optimizer=None, reward_mix=None):
         if encoder_optimizer is not None:
             raise NotImplementedError("self-critical training with a trainable embed Linear: the features are "
                                       "computed once, without a graph")
         super().__init__(encoder, decoder, optimizer, refs, decoder.linear.weight.shape[0], ctx, num_samples,
-                         temperature, top_k, baseline, max_steps, score_end, graph, start_idx, end_idx, pad_idx)
+                         temperature, top_k, baseline, max_steps, score_end, graph, start_idx, end_idx, pad_idx,
+                         reward_mix)
 
     def _sampler(self, n, temperature, top_k):
         return BaselineBatchedSampler(self.decoder, n, temperature, top_k)
@@ -417,7 +463,8 @@ class AttentionSelfCriticalStep(_SelfCriticalStep):
     dense embeddings."""
 
     def __init__(self, encoder, decoder, optimizer, refs, ctx=None, num_samples=5, temperature=1.0, top_k=0,
-                 baseline="mean", max_steps=20, score_end=True, graph=False, start_idx=1, end_idx=2, pad_idx=0):
+                 baseline="mean", max_steps=20, score_end=True, graph=False, start_idx=1, end_idx=2, pad_idx=0,
+                 reward_mix=None):
         from .decoder_group import N_MAX
         if getattr(decoder, "use_bert", False):
             raise NotImplementedError("self-critical training with BERT / dense word embeddings: the sampler has "
@@ -430,7 +477,7 @@ class AttentionSelfCriticalStep(_SelfCriticalStep):
         if int(num_samples) > N_MAX:
             raise ValueError(f"num_samples must be <= {N_MAX} (the rows of an image one workgroup serves)")
         super().__init__(encoder, decoder, optimizer, refs, decoder.fc.weight.shape[0], ctx, num_samples, temperature,
-                         top_k, baseline, max_steps, score_end, graph, start_idx, end_idx, pad_idx)
+                         top_k, baseline, max_steps, score_end, graph, start_idx, end_idx, pad_idx, reward_mix)
         named = dict(decoder.named_parameters())
         self.need = [k for k in PNAMES if named[k].requires_grad]
         self._named = named

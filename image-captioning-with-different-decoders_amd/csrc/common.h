@@ -126,3 +126,14 @@ __device__ __forceinline__ T slab_sum(const T* __restrict__ p, int S, long long 
 __device__ __forceinline__ float dot4(float4 a, float4 b) {
   return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;
 }
+
+// first index in [lo, hi) whose key is >= key (the sorted n-gram tables of scst.hip and score.hip)
+__device__ __forceinline__ int key_lower_bound(const unsigned long long* __restrict__ k, int lo, int hi,
+                                               unsigned long long key) {
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (k[mid] < key) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}

@@ -58,17 +58,6 @@ __global__ void __launch_bounds__(1024) rollout_pack_kernel(const int* __restric
   }
 }
 
-// first index in [lo, hi) whose key is >= key
-__device__ __forceinline__ int key_lower_bound(const unsigned long long* __restrict__ k, int lo, int hi,
-                                               unsigned long long key) {
-  while (lo < hi) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (k[mid] < key) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
 __global__ void __launch_bounds__(256) cider_reward_kernel(
     const int* __restrict__ tokens, int T, int R, int n, const int* __restrict__ lens,
     const int* __restrict__ img_key, int n_images, int end_idx, int score_end,

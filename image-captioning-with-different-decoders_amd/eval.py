@@ -8,9 +8,10 @@ The reference's arguments are kept: ``checkpoint`` (a file in ./checkpoints), ``
 ``--max_caption_length``, ``--print_freq``. Added: ``--batch_size`` (1, the default, runs the reference's
 one-caption-at-a-time ``evaluate``; larger runs ``evaluate_batched`` of models.attention / models.baseline,
 whose per-caption numbers are the same),``--synthetic_size`` / ``--vocab_size`` / ``--synthetic_len`` (COCO-shaped synthetic
-captions of ragged lengths instead of the COCO 'val' set) and ``--trusted_checkpoint`` (as train.py: the
-reference's whole-module checkpoints are pickles). The metrics are printed and written to
-<PathConfig.eval_data>/<checkpoint stem>.json.
+captions of ragged lengths instead of the COCO 'val' set), ``--scorer device`` (the batched pass counts BLEU /
+ROUGE-L / CIDEr on the HIP device, capmi.devscore; ``host``, the default, is capmi.scoring) and
+``--trusted_checkpoint`` (as train.py: the reference's whole-module checkpoints are pickles). The metrics are
+printed and written to <PathConfig.eval_data>/<checkpoint stem>.json.
 """
 import argparse
 import json
@@ -48,6 +49,9 @@ def parse_args(argv=None):
     parser.add_argument('--synthetic_len', type=int, default=25, help='longest synthetic caption.')
     parser.add_argument('--trusted_checkpoint', type=bool, default=False,
                         help='checkpoint is a whole-module pickle you wrote yourself (load with weights_only=False).')
+    parser.add_argument('--scorer', type=str, default='host', choices=['host', 'device'],
+                        help='where the batched pass scores its captions: capmi.scoring on the host or '
+                             'capmi.devscore on the HIP device.')
     args = parser.parse_args(argv)
     if args.batch_size < 1:
         parser.error('--batch_size must be >= 1')

@@ -489,7 +489,11 @@ def evaluate_batched(device, args, encoder, decoder, dataset=None, batch_size=64
                 drain()
                 print(f'Batch {batch_idx+1}/{num_batches}, Loss {accum_loss.avg():.4f}')
         drain()
-    metrics = caption_scores(references, hypotheses)
+    if getattr(args, "scorer", "host") == "device":  # the counting on the device (capmi.devscore)
+        from capmi.devscore import caption_scores_device
+        metrics = caption_scores_device(references, hypotheses, device)
+    else:
+        metrics = caption_scores(references, hypotheses)
     metrics.update(losses=losses, loss=accum_loss.avg(), top1_acc=hits1 / max(rows, 1), top5_acc=hits5 / max(rows, 1),
                    references=references, hypotheses=hypotheses)
     print(f'Checkpoint {getattr(args, "checkpoint", None)} finished evaluation in '

@@ -300,7 +300,8 @@ def train_self_critical(device, args):
 
 def self_critical_data(device, args):
     """The data side of self-critical training, for either captioner: (ctx, device, the training set, its (image,
-    caption, key) items, the ``CiderRefs`` of its captions grouped by image, END appended)."""
+    caption, key) items, the ``CiderRefs`` of its captions grouped by image, END appended; with
+    ``args.sc_reward_mix`` set, the ``capmi.devscore.ScoreRefs`` of the same captions)."""
     from capmi import dist as cdist
     from capmi.data import synthetic_requested
     from capmi.scst import MAX_REF_WORDS, CiderRefs
@@ -320,8 +321,11 @@ def self_critical_data(device, args):
     vocab = dataset.vocab
     end_idx = vocab(END_TOKEN)
     special = {vocab(PAD_TOKEN), vocab(START_TOKEN), end_idx}
-    refs = CiderRefs.build([[[w for w in cap.tolist() if w not in special][:MAX_REF_WORDS] for cap in base.references(k)]
-                            for k in range(n_images)], end_idx=end_idx, device=device)
+    tables = CiderRefs
+    if getattr(args, "sc_reward_mix", None) is not None:  # a mixed reward reads the BLEU / ROUGE-L tables too
+        from capmi.devscore import ScoreRefs as tables
+    refs = tables.build([[[w for w in cap.tolist() if w not in special][:MAX_REF_WORDS] for cap in base.references(k)]
+                         for k in range(n_images)], end_idx=end_idx, device=device)
     return ctx, device, base, dataset, refs
 
 
@@ -359,10 +363,11 @@ def self_critical_loop(args, ctx, device, base, dataset, refs, encoder, decoder,
                                          pin_memory=pin, persistent_workers=args.workers > 0 and cache is not None)
     feed = ImageFeeder(device, cache)
     decoder_optimizer = Adam(filter(lambda p: p.requires_grad, decoder.parameters()), lr=args.decoder_lr)
+    mix = getattr(args, "sc_reward_mix", None)  # weights of CIDEr-D, BLEU-4, ROUGE-L (capmi.scst); no train.py flag
     step = step_class(encoder, decoder, decoder_optimizer, refs, ctx, num_samples=args.sc_samples,
                       temperature=args.sc_temperature, top_k=args.sc_top_k, baseline=args.sc_baseline,
                       max_steps=args.sc_max_len, score_end=True, graph=os.environ.get("CAPMI_TRAIN_GRAPH", "1") != "0",
-                      start_idx=start_idx, end_idx=end_idx, pad_idx=pad_idx)
+                      start_idx=start_idx, end_idx=end_idx, pad_idx=pad_idx, reward_mix=mix)
     owner.last_step = step
     if pin and args.workers > 0:  # the loader's pin-memory thread allocates while a step is being captured
         step.capture_error_mode = "thread_local"
@@ -375,7 +380,7 @@ def self_critical_loop(args, ctx, device, base, dataset, refs, encoder, decoder,
         if sampler is not None:
             sampler.set_epoch(epoch)
         batch_losses, batch_rewards, pending = [], [], []
-        accum = [AccumulatingMetric(), AccumulatingMetric(), AccumulatingMetric()]
+        accum = [AccumulatingMetric() for _ in range(3 if mix is None else 6)]
         accum_time = AccumulatingMetric()
         start = time.time()
         for batch_idx, (imgs, keys) in enumerate(loader):
@@ -384,21 +389,26 @@ def self_critical_loop(args, ctx, device, base, dataset, refs, encoder, decoder,
             it += 1
             # the step's own buffers: the next call reuses them
             pending.append(torch.cat([loss.detach(), step.last["reward_mean"],
-                                      step.last["greedy_reward_mean"] if greedy else loss.detach()]))
+                                      step.last["greedy_reward_mean"] if greedy else loss.detach()]
+                                     + ([step.last[k].mean().reshape(1) for k in ("cider", "bleu4", "rouge_l")]
+                                        if mix is not None else [])))
             if batch_idx % args.print_freq == 0 or batch_idx == num_batches - 1:
                 torch.cuda.synchronize()
                 K.sk_check()
-                for l, r, g in torch.stack(pending).tolist():
+                for l, r, g, *parts in torch.stack(pending).tolist():
                     batch_losses.append(l)
                     batch_rewards.append(r)
-                    for a, v in zip(accum, (l, r, g)):
+                    for a, v in zip(accum, (l, r, g, *parts)):
                         a.update(v)
                 pending = []
                 accum_time.update(time.time() - start)
                 if ctx.rank == 0 and batch_idx % args.print_freq == 0:
                     print(f'Epoch {epoch+1}/{args.epochs}, Batch {batch_idx+1}/{num_batches}, '
                           f'Loss {accum[0].avg():.4f}, Reward {accum[1].avg():.4f}, '
-                          + (f'Greedy {accum[2].avg():.4f}, ' if greedy else '') + f'Time: {accum_time.val:.4f}')
+                          + (f'Greedy {accum[2].avg():.4f}, ' if greedy else '')
+                          + (f'CIDEr-D {accum[3].avg():.4f}, BLEU-4 {accum[4].avg():.4f}, '
+                             f'ROUGE-L {accum[5].avg():.4f}, ' if mix is not None else '')
+                          + f'Time: {accum_time.val:.4f}')
             start = time.time()
         epoch_losses.append(batch_losses)
         epoch_rewards.append(batch_rewards)
@@ -553,7 +563,11 @@ def evaluate_batched(device, args, encoder, decoder, dataset=None, batch_size=64
                 drain()
                 print(f'Batch {batch_idx+1}/{num_batches}, Loss {accum_loss.avg():.4f}')
         drain()
-    metrics = caption_scores(references, hypotheses)
+    if getattr(args, "scorer", "host") == "device":  # the counting on the device (capmi.devscore)
+        from capmi.devscore import caption_scores_device
+        metrics = caption_scores_device(references, hypotheses, device)
+    else:
+        metrics = caption_scores(references, hypotheses)
     metrics.update(losses=losses, loss=accum_loss.avg(), top1_acc=hits1 / max(rows, 1), top5_acc=hits5 / max(rows, 1),
                    references=references, hypotheses=hypotheses)
     print(f'Checkpoint {getattr(args, "checkpoint", None)} finished evaluation in '

@@ -750,6 +750,49 @@ int capmi_pg_ce_fwd_bwd(const float* logits, const long long* caps, int B, int T
                         float* loss_rows, float* dlogits, int dl_time_major, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Caption metrics on the token table (csrc/score.hip): BLEU-1..4 and ROUGE-L per hypothesis row, and the weighted
+ * mix of the three rewards. New symbols only, added without an ABI bump (purely additive). Integer sums, no
+ * atomics; every argument is checked before any launch.
+ * ---------------------------------------------------------------------- */
+#define CAPMI_SCORE_STATS 14
+/* tokens, T, R, n, lens, img_key, n_images, V, end_idx, score_end: as capmi_cider_reward reads them; n-gram keys in
+ * its format. Tables, built once by the host (capmi.devscore.ScoreRefs):
+ *   bleu_keys / bleu_cnt [n_keys]  per image the distinct 1..4-gram keys of all its references, ascending, and the
+ *                                  maximum count of the key over those references; entries bleu_off[k] ..
+ *                                  bleu_off[k + 1] - 1 belong to image k
+ *   ref_tok [n_tok], ref_off [refs + 1], ref_len [refs]   every image's DISTINCT references as flat tokens:
+ *                                  reference j is ref_tok[ref_off[j] .. ref_off[j + 1] - 1], ref_len[j] = its
+ *                                  number of words, at most 64
+ *   rimg_off [n_images + 1]        the distinct references of image k are rimg_off[k] .. rimg_off[k + 1] - 1
+ * Per row r, with len its hypothesis's words (score_end == 0 drops a final end_idx):
+ *   stats[r][0..3]   matches of orders 1..4: sum over the hypothesis's distinct n-grams of min(count, max count)
+ *   stats[r][4..7]   guesses max(0, len - k), k = 0..3
+ *   stats[r][8]      len;  stats[r][9] the reference length closest to len (the shorter on a tie)
+ *   stats[r][10]     lcs_p: the largest LCS over the references
+ *   stats[r][11..12] (lcs_r, len_r) of the reference with the largest lcs / len_r, compared by integer cross-
+ *                    multiplication, the shorter reference on equal ratios
+ *   stats[r][13]     the hypothesis's length as ROUGE-L counts it: an empty sentence is one empty token, so max(1,
+ *                    len); len_r likewise; that token matches only another empty sentence
+ *   bleu[r][0..3]    sentence-level BLEU-1..4 of this one hypothesis (reference eval_func/bleu: clipped counts, the
+ *                    constants 1e-15 / 1e-9, brevity penalty), rouge[r] its ROUGE-L F (beta 1.2, reference
+ *                    eval_func/rouge); both computed in fp64 from the integers and rounded once
+ * Columns 0..9 summed over rows give corpus BLEU; the mean of the rows' F corpus ROUGE-L. One workgroup per row; a
+ * row's outputs depend on that row and the tables alone. img_key outside [0, n_images): stats -1, bleu and rouge
+ * NaN. CAPMI_EINVAL on a NULL pointer (bleu_keys / bleu_cnt may be NULL when n_keys == 0, ref_tok when n_tok == 0),
+ * T outside 1..64, R < 1, n < 1, R % n != 0, n_images < 1, V < 1, end_idx < 0, n_keys < 0 or n_tok < 0;
+ * CAPMI_ERANGE on V > 65534 or R * CAPMI_SCORE_STATS >= 2^31. */
+int capmi_caption_stats(const int* tokens, int T, int R, int n, const int* lens, const int* img_key, int n_images,
+                        int V, int end_idx, int score_end, const unsigned long long* bleu_keys, const int* bleu_cnt,
+                        int n_keys, const int* bleu_off, const int* ref_tok, int n_tok, const int* ref_off,
+                        const int* ref_len, const int* rimg_off, int* stats, float* bleu, float* rouge, void* stream);
+/* reward[r] = (w_cider cider[r] + w_bleu4 bleu4[r * bleu_stride]) + w_rouge rouge[r], evaluated in fp64 in that
+ * order and rounded once; a NaN input gives NaN. bleu_stride 4 reads column 3 of capmi_caption_stats's bleu from
+ * bleu + 3. One launch. CAPMI_EINVAL on a NULL pointer, R < 1, bleu_stride < 1 or a NaN weight; CAPMI_ERANGE on
+ * R * bleu_stride >= 2^31. */
+int capmi_reward_mix(const float* cider, const float* bleu4, long long bleu_stride, const float* rouge, int R,
+                     double w_cider, double w_bleu4, double w_rouge, float* reward, void* stream);
+
+/* ------------------------------------------------------------------------
  * Attention backward over row groups that share one image's features (csrc/att_group.hip): the teacher-forced
  * pass over the R = B*n sampled captions of self-critical training, the backward of capmi_beam_att_fwd. Row layout
  * as there: image i owns rows i*n .. i*n+n-1, 1 <= n <= 16; every row is live. enc [B][P][E] and att_enc [B][P][A]

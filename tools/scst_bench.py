@@ -50,7 +50,8 @@ def timed(fn, repeats):
     return statistics.median(out)
 
 
-def setup(graph):
+def setup(graph, reward_mix=None):
+    """``reward_mix``: the step trains on that mix and the table is a capmi.devscore.ScoreRefs (tools/score_bench.py)."""
     import torch
 
     import baseline_cases as BLC
@@ -66,7 +67,11 @@ def setup(graph):
     for seed in range(100, 100 + REFS):
         for b, per in enumerate(one.sample(feats, start, end, max_steps=MAX_STEPS, seed=seed)):
             refs[b].append([w for w in per[0]["seq"] if w not in (start, end, 0)])
-    table = CiderRefs.build(refs, end_idx=end, device=dev)
+    if reward_mix is not None:
+        from capmi.devscore import ScoreRefs
+        table = ScoreRefs.build(refs, end_idx=end, device=dev)
+    else:
+        table = CiderRefs.build(refs, end_idx=end, device=dev)
     opt = Adam([q for q in dec.parameters() if q.requires_grad], lr=1e-4)
     opt.set_clip(5.0)
 
@@ -75,7 +80,7 @@ def setup(graph):
             return x
 
     step = BaselineSelfCriticalStep(Identity(), dec, opt, table, num_samples=N, max_steps=MAX_STEPS, graph=graph,
-                                    start_idx=start, end_idx=end, pad_idx=0)
+                                    start_idx=start, end_idx=end, pad_idx=0, reward_mix=reward_mix)
     keys = torch.arange(B, dtype=torch.int32, device=dev)
     return step, feats, keys, table
 
