@@ -308,7 +308,7 @@ def gemm_x3_kernel_name(prob, amode, tile=CAPMI_TILE_AUTO):
 
 def gemm_bf16_kernel_name(prob, amode, tile=CAPMI_TILE_AUTO):
     """The instantiation gemm_bf16(prob, amode, workspace, tile) launches (capmi_gemm_sk_plan with
-    CAPMI_GEMM_BF16_IO: the launcher's own plan, gemm.hip bf16_io_plan)."""
+    CAPMI_GEMM_BF16_IO: the launcher's own plan, gemm_plan.hip plan_bf16_io)."""
     v = [ctypes.c_int(0) for _ in range(5)]
     call("capmi_gemm_sk_plan", ctypes.byref(prob), amode, CAPMI_B_NMAJOR_W, tile, CAPMI_GEMM_BF16_IO,
          *[ctypes.byref(x) for x in v])

@@ -467,7 +467,7 @@ class EncoderRunner:
             prob, mode = K.problem_bf16(rows, co, Kd, x, 0, w, Kd, out, co, stats=stats, conv=geo), AC
         launch = lambda: K.gemm_bf16(prob, mode, self._ws["sk"], K.TILE_AUTO)  # noqa: E731
         if self.conv_hook is not None:
-            key = K.gemm_bf16_kernel_name(prob, mode)  # the launcher's own plan (gemm.hip bf16_io_plan)
+            key = K.gemm_bf16_kernel_name(prob, mode)  # the launcher's own plan (gemm_plan.hip plan_bf16_io)
             self.conv_hook(tag, 2.0 * rows * co * Kd, launch, key)
         else:
             launch()

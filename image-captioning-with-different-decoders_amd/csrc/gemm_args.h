@@ -1,4 +1,4 @@
-// Launch descriptor shared by the GEMM kernels (gemm.hip, gemm_nt.hip).
+// Launch descriptor shared by the GEMM kernels (gemm*.hip) and their host planner (gemm_plan.hip).
 #pragma once
 #include "common.h"
 
@@ -20,11 +20,11 @@ struct GemmArgs {
   float* sk_part;        // [workers][BM*BN] parked k-prefix partials
   int* sk_flags;         // [workers + 1], zero between launches; [workers] = spin-timeout flag
   int tile_cols_first;   // x3p: tile t = (tm, tn) as tm = t % tiles_m, tn = t / tiles_m (column-major)
-  // x3 kernels (gemm_x3 / x3p / x3d): the store-only epilogue applies (plain_epilogue() below): C = A.B
+  // x3 kernels (gemm_x3 / x3p / x3d): the store-only epilogue applies (plain_epilogue(), gemm_plan.hip): C = A.B
   // stored through one buffer descriptor with per-row 32-bit offsets computed once per tile -- no
   // per-element 64-bit address, bounds branch, alpha / bias / beta / relu (round 3)
   int plain_epi;
-  // x3d (round 4): the two-deep A pipeline for this launch (the planner's rule, gemm.hip x3d_plan)
+  // x3d (round 4): the two-deep A pipeline for this launch (the planner's rule, gemm_plan.hip plan_x3d)
   int x3d_pipe;
 };
 
@@ -99,28 +99,20 @@ __device__ __forceinline__ long long remap(long long r, long long r1, long long 
   return r1 > 0 ? (r % r1) * ld + (r / r1) * s2 : r * ld;
 }
 
-// Host: does problem p take the store-only epilogue of the x3 kernels with BN-wide column tiles?
-// (C = A.B (+ beta C) exactly: no alpha / bias / relu / row remap; whole column tiles; C addressable with
-// 32-bit byte offsets; rows past M read zeros in A, so their accumulators add nothing to the BN sums)
-inline int plain_epilogue(const capmi_gemm_problem& p, int bn) {
-  static const bool off = [] {  // CAPMI_X3_PLAIN_EPI=0: the general epilogue everywhere (A/B arm)
-    const char* e = getenv("CAPMI_X3_PLAIN_EPI");
-    return e && e[0] == '0';
-  }();
-  // 1: C = A.B; 2: C = A.B + beta C (read-modify-write through the same offsets; the fine-tune 1x1 data
-  // gradients accumulate into the block input's gradient)
-  const bool ok = !off && p.alpha == 1.f && p.alpha_ptr == nullptr && p.bias == nullptr && p.bias2 == nullptr &&
-                  !p.relu && p.c_r1 <= 0 && p.ksplit == 1 && p.N % bn == 0 && p.ldc >= p.N &&
-                  (long long)p.M * p.ldc * 4 < (1LL << 31);
-  return ok ? (p.beta == 0.f ? 1 : 2) : 0;
-}
-
+// generic (v1) kernel (gemm.hip): 128x128 (bm = 128) or 64x64 tiles of k-depth kGemmV1BK, every amode / bmode pair
+// the v2 kernel does not take; vec: every operand row is 16-byte aligned (float4 loads)
+constexpr int kGemmV1BK = 16;
+int gemm_v1_launch(const GemmArgs& a, int amode, int bmode, int bm, bool vec, int blocks, hipStream_t s);
 // v2 kernel: A K-major dense / NHWC conv / NHWC4 conv1 / M-major (k rows), B = W[N][K] or k rows;
 // BM x BN in {128x128, 128x64, 64x64}
 int gemm_nt_launch(const GemmArgs& a, int amode, int bmode, int bm, int bn, int blocks, hipStream_t s,
                    int terms = 0, int nt = 256);
 // bf16-in/bf16-out conv GEMM (gemm_bf16.hip): BM = 128, BN in {128, 64}, amode 0 (dense) / 2 (conv)
 int gemm_bf16_launch(const GemmArgs& a, int amode, int bm, int bn, int blocks, hipStream_t s, int stages);
+// its LDS-DMA ring form (ST stages >= 2, not stream-K) and workgroup size: 512 threads on the ring's 128-column
+// tiles, else 256 (gemm_bf16.hip's ST notes); the kernel's launch bounds and the plan query both read these
+constexpr bool bf16_dma(int ST, bool SK) { return ST >= 2 && !SK; }
+constexpr int bf16_threads(int BN, int ST, bool SK) { return bf16_dma(ST, SK) && BN == 128 ? 512 : 256; }
 // fp32-accurate 3-way bf16 split GEMM (gemm_x3.hip): BM = 128, BN in {128, 64}, 512 threads,
 // amode 0 (dense) / 2 (conv, optional prologue)
 int gemm_x3_launch(const GemmArgs& a, int amode, int bn, int blocks, hipStream_t s);
@@ -154,9 +146,3 @@ int gemm_x3w_launch(const GemmArgs& a, int bmode, int blocks, hipStream_t s, int
 int gemm_x3c_launch(const capmi_gemm_problem& p, int tiles, hipStream_t s);
 int gemm_x3c_max_width();
 bool gemm_x3c_band_fits(const capmi_gemm_problem& p);
-// resident workgroups per CU of the NT kernel for a tile shape (LDS / register bound)
-// (terms 3: three bf16 LDS planes per operand, 60 KB for 64x64 and >= 90 KB for the larger tiles)
-inline int gemm_nt_wg_per_cu(int bm, int bn, int terms = 0) {
-  if (terms == 3) return bm == 64 && bn == 64 ? 2 : 1;
-  return bm == 64 && bn == 64 ? 4 : 2;
-}

@@ -56,8 +56,7 @@ __device__ __forceinline__ void vm_barrier() {
 //    (waves 2 x 4, wave tile 64 x 32), so a SIMD holds two waves of a workgroup: 75 VGPRs instead of the register
 //    form's 212, two workgroups per CU at ST = 2 (64 KiB of LDS each), one at ST = 4 (128 KiB).
 // Otherwise 256 threads (waves 2 x 2, wave tile 64 x BN / 2).
-constexpr bool bf16_dma(int ST, bool SK) { return ST >= 2 && !SK; }
-constexpr int bf16_threads(int BN, int ST, bool SK) { return bf16_dma(ST, SK) && BN == 128 ? 512 : 256; }
+// (bf16_dma and bf16_threads: gemm_args.h, shared with the planner)
 constexpr int bf16_waves(int BM, int BN, int ST, bool SK) {  // waves per SIMD the LDS leaves room for
   return ST == 1 ? 4 : !bf16_dma(ST, SK) ? 2 : (160 * 1024 / (ST * (BM + BN) * 128)) * bf16_threads(BN, ST, SK) / 256;
 }

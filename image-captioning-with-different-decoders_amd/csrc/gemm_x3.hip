@@ -432,7 +432,7 @@ void launch_x3(const GemmArgs& a, int amode, bool pro, int blocks, hipStream_t s
       CAPMI_KLAUNCH((gemm_x3_kernel<BN, 2, true, SK>), g, b, 0, s, a);
     else
       CAPMI_KLAUNCH((gemm_x3_kernel<BN, 2, false, SK>), g, b, 0, s, a);
-  } else {  // dense A: no prologue (x3_plan)
+  } else {  // dense A: no prologue (plan_x3)
     CAPMI_KLAUNCH((gemm_x3_kernel<BN, 0, false, SK>), g, b, 0, s, a);
   }
 }

@@ -616,7 +616,7 @@ gemm_x3p_kernel(const GemmArgs args) {
         // to memory per lane -- the fine-tune 1x1 data gradients ran 92 us against 51 for the same GEMM shape.
         // (All 64 ahead of the stores spilled this kernel's registers.)
         // The stream-K forms sit at the 256-register cap and spill with those loads in flight: they keep the
-        // interleaved form, and the planner runs beta problems data-parallel (x3d_plan).
+        // interleaved form, and the planner runs beta problems data-parallel (plan_x3d).
 #pragma unroll
         for (int j = 0; j < JN; ++j) {
           csum4[j] = 0.f;

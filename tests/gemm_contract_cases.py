@@ -154,7 +154,7 @@ def layout(case, i=0):
     L.c_split_stride = (L.c_rows + GUARD_ROWS) * L.c_width + SLAB_GAP if L.ksplit > 1 else 0
     slab = (L.c_rows + GUARD_ROWS) * L.c_width + SLAB_GAP
     L.c_numel = L.c_off + L.ksplit * slab
-    # k range of slab z (gemm_plan: the chunk rounded up to the v2 kernel's k-tile of 32)
+    # k range of slab z (plan_nt_group, csrc/gemm_plan.hip: the chunk rounded up to the v2 kernel's k-tile of 32)
     kc = -(-K // L.ksplit)
     kc = -(-kc // 32) * 32
     L.k_ranges = [(min(K, z * kc), min(K, (z + 1) * kc)) for z in range(L.ksplit)]
@@ -469,7 +469,7 @@ def _x3_cases(cases):
                 add("x3p", X3P, a, False, 128, sk, cfg, f"gemm_x3p_kernel<{a}, {b(sk)}, 32, false, false>", geom)
                 for pro in (False, True):
                     if cfg == "plain_beta1" and sk:
-                        continue  # x3d runs C = A.B + beta C data-parallel whatever the grid (x3d_plan)
+                        continue  # x3d runs C = A.B + beta C data-parallel whatever the grid (plan_x3d)
                     add("x3d", X3D, a, pro, 128, sk, cfg, f"gemm_x3p_kernel<{a}, {b(sk)}, 32, true, {b(pro)}>", geom)
 
 
@@ -611,8 +611,9 @@ REFUSALS = _refusals()
 
 # launch sites of csrc/gemm_nt.hip that no host path reaches (kernel, AMODE, BMODE, PRO, TERMS) -> why
 UNREACHABLE = {
-    ("gemm_nt_kernel", 1, 0, False, 0): "gemm_plan keeps A-as-k-rows x W[N][K] off the v2 kernel (nt_ok): it runs "
-                                        "the generic kernel, which the generic-*-a1b0 cases pin",
+    ("gemm_nt_kernel", 1, 0, False, 0): "plan_nt_group (gemm_plan.hip) keeps A-as-k-rows x W[N][K] off the v2 "
+                                        "kernel (nt_ok): it runs the generic kernel, which the generic-*-a1b0 "
+                                        "cases pin",
     ("gemm_nts_kernel", 0, 0, False, 1): "launch_bmbn sends the bf16 forward modes (terms 1, B = W[N][K]) to "
                                          "launch_sk_bf16, which the bf16-* cases pin",
 }

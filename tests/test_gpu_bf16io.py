@@ -153,7 +153,7 @@ def test_bf16_elementwise():
 ])
 def test_bf16io_layer4_exact_shapes(H, Cin, Cout, k, s, name):
     """layer4's convs at batch 64 run 128x64 tiles on grids of 128x128 tiles that fill at most half
-    the CUs (round 5), since round 6 on the four-deep DMA ring (gemm.hip bf16_io_plan) -- checked element-wise at their
+    the CUs (round 5), since round 6 on the four-deep DMA ring (gemm_plan.hip plan_bf16_io) -- checked element-wise at their
     exact shapes, the instantiation asserted through the launcher's own plan. fp64 reference on the device (im2col +
     GEMM)."""
     from capmi import kernels as K

@@ -1,7 +1,7 @@
 """GPU: the kernel names the bench prices are the instantiations the launcher runs.
 
 bench.py attributes conv time to a kernel key (roofline.kernel, the PMC traffic lookup) that comes from the planner's
-plan query (capmi_gemm_sk_plan; for the bf16 convs since ABI 25 the launcher's own bf16_io_plan). Here every conv
+plan query (capmi_gemm_sk_plan; for the bf16 convs since ABI 25 the launcher's own plan_bf16_io). Here every conv
 GEMM of the benchmarked configs at batch 64 -- config 2 (x3 forward), config 4 (x3 fine-tune forward and layer2-4
 backward: dgrad / wgrad) and config 5 (bf16 forward) -- goes through the encoder's conv hook, and the key it is
 priced under must equal the demangled instantiation the launch actually ran (capmi_last_launch_name: the kernel
