@@ -802,7 +802,7 @@ def lstm_step_fwd(R, M, H, h_out, c_out, *, pre=None, ld_pre=0, x=None, ld_x=0, 
 
 
 # --------------------------------------------------------------------------------------
-# baseline (LSTM) captioner in training (csrc/baseline_step.hip, csrc/baseline_train.hip)
+# baseline (LSTM) captioner in training (csrc/baseline_step.hip, csrc/loss.hip)
 # --------------------------------------------------------------------------------------
 def lstm_step_fwd_train(R, M, H, h_out, c_out, act_out, *, pre=None, ld_pre=0, x=None, ld_x=0, h_prev=None, ld_h=0,
                         c_prev=None, ld_c=0, w_ih=None, w_hh=None, b_ih=None, b_hh=None):

@@ -1,10 +1,10 @@
-// Attention-decoder step kernels (forward + backward through time), loss kernels.
+// Attention-decoder step kernels (forward + backward through time), the alpha regulariser.
 //
 // Reference: models/attention.py
 //   SoftAttention.forward                    :43-61   (ReLU score, softmax over the 196 slots)
 //   AttentionDecoder.init_hidden_state       :151-164
 //   AttentionDecoder.forward time loop       :260-281 (gate :270-271, LSTMCell :277-278, fc :279)
-//   loss                                     :401-414 (CE over packed rows incl. pads, alpha reg)
+//   loss                                     :401-414 (alpha reg here; CE over packed rows incl. pads: loss.hip)
 //
 // Layout: per-step tensors are time-major [t][b][...]; the API outputs predictions /
 // alphas keep the reference's batch-major (B,T,V) / (B,T,P). Each kernel's grid has
@@ -361,70 +361,6 @@ extern "C" int capmi_mask_rows_tb(float* x, const int* bt, int T, int B, int col
 }
 
 // --------------------------------------------------------------------------------------
-// Cross entropy over the (B,T,V) logits: one workgroup per row, online max/sum, then the
-// gradient (softmax - onehot)/nrows in the same launch (the row is L2-hot).
-// --------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) ce_fwd_bwd_kernel(
-    const float* __restrict__ logits, const long long* __restrict__ caps, int B, int T, int L,
-    int V, const int* __restrict__ bt, float inv_n, float* __restrict__ loss_rows,
-    float* __restrict__ lse_out, float* __restrict__ dlogits, int tm, const float* __restrict__ gscale) {
-  __shared__ float red[16];
-  const int r = blockIdx.x;  // r = b*T + t
-  const int b = r / T, t = r - b * T;
-  const bool active = bt == nullptr || b < bt[t];
-  const long long drow = tm ? ((long long)t * B + b) : r;
-  if (!active) {
-    if (threadIdx.x == 0) {
-      loss_rows[r] = 0.f;
-      if (lse_out) lse_out[r] = 0.f;
-    }
-    if (dlogits)
-      for (int v = threadIdx.x; v < V; v += 256) dlogits[drow * V + v] = 0.f;
-    return;
-  }
-  const float* x = logits + (long long)r * V;
-  float m = -INFINITY, s = 0.f;
-  for (int v = threadIdx.x; v < V; v += 256) {
-    const float xv = x[v];
-    if (xv > m) {
-      s = s * expf(m - xv) + 1.f;
-      m = xv;
-    } else {
-      s += expf(xv - m);
-    }
-  }
-  const float gm = block_max(m, red);
-  s = (m == -INFINITY) ? 0.f : s * expf(m - gm);
-  s = block_sum(s, red);
-  const float lse = gm + logf(s);
-  const long long tgt = caps[(long long)b * L + t + 1];
-  if (threadIdx.x == 0) {
-    loss_rows[r] = lse - x[tgt];
-    if (lse_out) lse_out[r] = lse;
-  }
-  if (dlogits) {
-    const float g = (gscale ? *gscale : 1.f) * inv_n;
-    for (int v = threadIdx.x; v < V; v += 256) {
-      const float pv = expf(x[v] - lse);
-      dlogits[drow * V + v] = (pv - (v == tgt ? 1.f : 0.f)) * g;
-    }
-  }
-}
-
-extern "C" int capmi_ce_fwd_bwd(const float* logits, const long long* caps, int B, int T, int L,
-                                int V, const int* bt, int nrows, float* loss_rows, float* lse,
-                                float* dlogits, int dl_time_major, const float* gscale,
-                                void* stream) {
-  CAPMI_REQUIRE(logits && caps && loss_rows && B > 0 && T > 0 && V > 0 && L > T && nrows > 0,
-                CAPMI_EINVAL);
-  hipLaunchKernelGGL(ce_fwd_bwd_kernel, dim3(B * T), dim3(256), 0, as_stream(stream), logits, caps,
-                     B, T, L, V, bt, 1.f / (float)nrows, loss_rows, lse, dlogits, dl_time_major,
-                     gscale);
-  CAPMI_LAUNCH_CHECK();
-  return 0;
-}
-
-// --------------------------------------------------------------------------------------
 // alpha regulariser ((alpha_c - sum_t alpha)^2).mean() and its gradient; one thread per (b, p)
 // --------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) alpha_reg_kernel(const float* __restrict__ alphas, int B,
@@ -456,28 +392,6 @@ extern "C" int capmi_alpha_reg(const float* alphas, int B, int T, int P, float a
   CAPMI_REQUIRE(alphas && B > 0 && T > 0 && P > 0, CAPMI_EINVAL);
   hipLaunchKernelGGL(alpha_reg_kernel, dim3(cdiv((long long)B * P, 256)), dim3(256), 0,
                      as_stream(stream), alphas, B, T, P, alpha_c, reg_part, dreg);
-  CAPMI_LAUNCH_CHECK();
-  return 0;
-}
-
-__global__ void __launch_bounds__(1024) loss_finalize_kernel(const float* __restrict__ rows, int n,
-                                                             float inv_n, const float* __restrict__ reg,
-                                                             int nreg, float* __restrict__ out) {
-  __shared__ float red[16];
-  float s = 0.f;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) s += rows[i];
-  s = block_sum(s, red);
-  float r = 0.f;
-  for (int i = threadIdx.x; i < nreg; i += blockDim.x) r += reg[i];
-  r = block_sum(r, red);
-  if (threadIdx.x == 0) out[0] = s * inv_n + r;
-}
-
-extern "C" int capmi_loss_finalize(const float* loss_rows, int n, int nrows, const float* reg_part,
-                                   int nreg, float* out, void* stream) {
-  CAPMI_REQUIRE(loss_rows && out && n > 0 && nrows > 0 && (nreg == 0 || reg_part), CAPMI_EINVAL);
-  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(1024), 0, as_stream(stream), loss_rows, n,
-                     1.f / (float)nrows, reg_part, nreg, out);
   CAPMI_LAUNCH_CHECK();
   return 0;
 }

@@ -2,7 +2,7 @@
 // token and target rank in one pass over the (B,T,V) logits, then the per-caption loss (CE mean over the
 // caption's own rows + its doubly-stochastic regulariser) and top-1 / top-5 counts.
 //
-//   capmi_eval_rows     : one workgroup per row r = b*T + t; online max/sum as ce_fwd_bwd_kernel, with the
+//   capmi_eval_rows     : one workgroup per row r = b*T + t; online max/sum as ce_rows_kernel (loss.hip), with the
 //                         (value, index) arg-max and the target's rank carried through the same loop
 //   capmi_eval_captions : one workgroup per caption, sums in a fixed order (bit-identical run to run)
 //   capmi_eval_rows_at / capmi_eval_captions_ce : the same two for the baseline model's loss (reference

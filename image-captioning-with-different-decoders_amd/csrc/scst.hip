@@ -1,6 +1,6 @@
 // Self-critical sequence training (SCST) on the sampler's token table: pack the rollouts into teacher-forcing
-// captions, score every hypothesis with CIDEr-D against its image's references, turn the rewards into advantages
-// and weight the cross-entropy rows by them. Nothing here copies to the host.
+// captions, score every hypothesis with CIDEr-D against its image's references and turn the rewards into
+// advantages. capmi_pg_ce_fwd_bwd (loss.hip) weights the cross-entropy rows by them. Nothing here copies to the host.
 //
 //   capmi_rollout_pack    tokens (T, R) int32 as capmi_sample_step leaves them (-1: the row had finished or the loop
 //                         had stopped) -> lens[r], caps (R, T + 1) int64 = [start, tok_0 .. tok_{len-1}, pad ..],
@@ -16,8 +16,6 @@
 //                         no barrier inside the reference loop; the four orders meet once at the end.
 //   capmi_scst_advantage  reward minus the mean of the image's other samples, or minus the greedy rollout's reward;
 //                         the batch means go to a two-float stats buffer. One workgroup, one launch.
-//   capmi_pg_ce_fwd_bwd   ce_ignore_fwd_bwd_kernel's per-row arithmetic (baseline_train.hip) with a row live by its
-//                         caption's length and weighted by its caption's advantage.
 //
 // All reductions are fp32 in one fixed order, no float atomics: a row's result depends on that row's inputs alone.
 #include "common.h"
@@ -164,60 +162,6 @@ __global__ void __launch_bounds__(1024) scst_advantage_kernel(const float* __res
   }
 }
 
-__global__ void __launch_bounds__(256) pg_ce_fwd_bwd_kernel(const float* __restrict__ logits,
-                                                            const long long* __restrict__ caps, int B, int T, int L,
-                                                            int V, int tgt_off, const int* __restrict__ lens,
-                                                            int t_first, const float* __restrict__ adv,
-                                                            const float* __restrict__ inv_count,
-                                                            float* __restrict__ logp_rows,
-                                                            float* __restrict__ loss_rows,
-                                                            float* __restrict__ dlogits, int tm) {
-  __shared__ float red[16];
-  const int r = blockIdx.x;  // r = b*T + t
-  const int b = r / T, t = r - b * T;
-  const long long tgt = caps[(long long)b * L + t + tgt_off];
-  const long long drow = tm ? ((long long)t * B + b) : r;
-  const bool live = t >= t_first && t - t_first < lens[b];
-  // a target outside [0, V) is never followed (capmi_ce_ignore_fwd_bwd)
-  if (!live || tgt < 0 || tgt >= V) {
-    if (threadIdx.x == 0) {
-      logp_rows[r] = 0.f;
-      loss_rows[r] = 0.f;
-    }
-    if (dlogits)
-      for (int v = threadIdx.x; v < V; v += 256) dlogits[drow * V + v] = 0.f;
-    return;
-  }
-  const float* x = logits + (long long)r * V;
-  float m = -INFINITY, s = 0.f;
-  for (int v = threadIdx.x; v < V; v += 256) {
-    const float xv = x[v];
-    if (xv > m) {
-      s = s * expf(m - xv) + 1.f;
-      m = xv;
-    } else {
-      s += expf(xv - m);
-    }
-  }
-  const float gm = block_max(m, red);
-  s = (m == -INFINITY) ? 0.f : s * expf(m - gm);
-  s = block_sum(s, red);
-  const float lse = gm + logf(s);
-  const float a = adv[b];
-  if (threadIdx.x == 0) {
-    const float lp = x[tgt] - lse;
-    logp_rows[r] = lp;
-    loss_rows[r] = -a * lp;
-  }
-  if (dlogits) {
-    const float g = a * *inv_count;
-    for (int v = threadIdx.x; v < V; v += 256) {
-      const float pv = expf(x[v] - lse);
-      dlogits[drow * V + v] = (pv - (v == tgt ? 1.f : 0.f)) * g;
-    }
-  }
-}
-
 }  // namespace
 
 extern "C" int capmi_rollout_pack(const int* tokens, int T, int R, long long start_idx, int end_idx,
@@ -260,20 +204,6 @@ extern "C" int capmi_scst_advantage(const float* reward, const float* greedy_rew
   CAPMI_REQUIRE((long long)B * n < (1LL << 31), CAPMI_ERANGE);
   hipLaunchKernelGGL(scst_advantage_kernel, dim3(1), dim3(1024), 0, as_stream(stream), reward, greedy_reward, B, n,
                      mode, adv, stats);
-  CAPMI_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int capmi_pg_ce_fwd_bwd(const float* logits, const long long* caps, int B, int T, int L, int V, int tgt_off,
-                                   const int* lens, int t_first, const float* adv, const float* inv_count,
-                                   float* logp_rows, float* loss_rows, float* dlogits, int dl_time_major,
-                                   void* stream) {
-  CAPMI_REQUIRE(logits && caps && lens && adv && logp_rows && loss_rows, CAPMI_EINVAL);
-  CAPMI_REQUIRE(B > 0 && T > 0 && V > 0 && tgt_off >= 0 && t_first >= 0 && L >= T + tgt_off, CAPMI_EINVAL);
-  CAPMI_REQUIRE(!dlogits || (inv_count && dlogits != logits), CAPMI_EINVAL);
-  CAPMI_REQUIRE((long long)B * T < (1LL << 31), CAPMI_ERANGE);
-  hipLaunchKernelGGL(pg_ce_fwd_bwd_kernel, dim3(B * T), dim3(256), 0, as_stream(stream), logits, caps, B, T, L, V,
-                     tgt_off, lens, t_first, adv, inv_count, logp_rows, loss_rows, dlogits, dl_time_major);
   CAPMI_LAUNCH_CHECK();
   return 0;
 }

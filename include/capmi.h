@@ -411,9 +411,11 @@ int capmi_counter_add(long long* counter, long long v, void* stream);
 int capmi_mask_rows_tb(float* x, const int* bt, int T, int B, int cols, long long ld, long long r1,
                        long long s2, void* stream);
 
-/* Loss (:401-414). rows r = b*T + t of logits (B,T,V); target = caps[b*L + t + 1].
+/* Loss (:401-414; csrc/loss.hip, the row arithmetic shared with capmi_ce_ignore_fwd_bwd and capmi_pg_ce_fwd_bwd).
+ * rows r = b*T + t of logits (B,T,V); target = caps[b*L + t + 1].
  * loss_rows[r] = lse - x[target]; dlogits (if non-NULL) = (softmax - onehot) * (*gscale) / nrows,
- * written at row t*B + b (time-major) when dl_time_major else b*T + t. Rows with t >= T_b skipped. */
+ * written at row t*B + b (time-major) when dl_time_major else b*T + t. A row with b >= bt[t] (bt non-NULL), or
+ * whose target is outside [0, V) (never followed), writes loss_rows[r] = 0, lse[r] = 0 and a zero dlogits row. */
 int capmi_ce_fwd_bwd(const float* logits, const long long* caps, int B, int T, int L, int V,
                      const int* bt, int nrows, float* loss_rows, float* lse, float* dlogits,
                      int dl_time_major, const float* gscale, void* stream);
@@ -660,7 +662,7 @@ int capmi_eval_captions_ce(const float* loss_rows, const int* rank, const int* l
 
 /* ------------------------------------------------------------------------
  * Baseline (LSTM) captioner in training (reference models/baseline.py:114-264; csrc/baseline_step.hip,
- * csrc/baseline_train.hip). New symbols only, nothing existing changed; added without an ABI bump (purely
+ * csrc/loss.hip). New symbols only, nothing existing changed; added without an ABI bump (purely
  * additive, as the BERT entries below).
  * ---------------------------------------------------------------------- */
 /* capmi_lstm_step_fwd that also writes act_out [R][4H] (contiguous) = (sig i | sig f | tanh g | sig o), the fp64
@@ -687,9 +689,10 @@ int capmi_lstm_step_bwd(const float* dh_lin, long long ld_dh, const float* dg_ne
  * count[0] (may be NULL) = #{targets != ignore_index}, inv_count[0] = 1 / count (count 0: +inf). */
 int capmi_count_targets(const long long* caps, int B, int T, int L, int tgt_off, long long ignore_index, int* count,
                         float* inv_count, void* stream);
-/* capmi_ce_fwd_bwd's per-row arithmetic: a live row writes loss_rows[r] = lse - x[target] and (dlogits non-NULL)
- * (softmax - onehot) * inv_count[0]; an ignored row (target == ignore_index, or outside [0, V): never followed)
- * writes loss_rows[r] = 0 and an all-zero dlogits row. dlogits row t*B + b when dl_time_major else b*T + t. */
+/* capmi_ce_fwd_bwd's per-row arithmetic (one definition, csrc/loss.hip): a live row writes loss_rows[r] =
+ * lse - x[target] and (dlogits non-NULL) (softmax - onehot) * inv_count[0]; an ignored row (target ==
+ * ignore_index, or outside [0, V): never followed) writes loss_rows[r] = 0 and an all-zero dlogits row. dlogits
+ * row t*B + b when dl_time_major else b*T + t. */
 int capmi_ce_ignore_fwd_bwd(const float* logits, const long long* caps, int B, int T, int L, int V, int tgt_off,
                             long long ignore_index, const float* inv_count, float* loss_rows, float* dlogits,
                             int dl_time_major, void* stream);
@@ -698,9 +701,9 @@ int capmi_ce_ignore_fwd_bwd(const float* logits, const long long* caps, int B, i
 int capmi_loss_finalize_dev(const float* loss_rows, int n, const float* inv_count, float* out, void* stream);
 
 /* ------------------------------------------------------------------------
- * Self-critical sequence training on sampled rollouts (csrc/scst.hip). New symbols only, nothing existing
- * changed; added without an ABI bump (purely additive). Every reduction is fp32 in one fixed order, no float
- * atomics; every argument is checked before any launch.
+ * Self-critical sequence training on sampled rollouts (csrc/scst.hip; capmi_pg_ce_fwd_bwd: csrc/loss.hip). New
+ * symbols only, nothing existing changed; added without an ABI bump (purely additive). Every reduction is fp32
+ * in one fixed order, no float atomics; every argument is checked before any launch.
  * ---------------------------------------------------------------------- */
 /* tokens (T, R) int32 as capmi_sample_step leaves its table: entry (t, r) is -1 where row r had finished or the
  * loop had stopped. lens[r] = the number of leading entries >= 0 up to and including the first end_idx, in 0..T;

@@ -1,4 +1,4 @@
-"""CPU: the baseline captioner's training entries (csrc/baseline_step.hip, csrc/baseline_train.hip) are declared,
+"""CPU: the baseline captioner's training entries (csrc/baseline_step.hip, csrc/loss.hip) are declared,
 exported and bound, and validate their arguments before any launch; models.baseline.train on a CPU device stays
 the reference loop and never loads the GPU step."""
 import ctypes

@@ -1,4 +1,4 @@
-"""GPU: the kernels behind the baseline captioner's training step (csrc/baseline_step.hip, csrc/baseline_train.hip).
+"""GPU: the kernels behind the baseline captioner's training step (csrc/baseline_step.hip, csrc/loss.hip).
 
 capmi_lstm_step_fwd_train: h / c are capmi_lstm_step_fwd's bits, act_out against the fp64 formula. capmi_lstm_step_bwd
 against the fp64 formula. Neither tolerance is a constant: in the same test the sequence the fused launch stands for

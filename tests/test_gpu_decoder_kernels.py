@@ -1,5 +1,5 @@
-"""GPU: the decoder's non-GEMM kernels (csrc/decoder.hip, the fused attention pair of csrc/decoder_step.hip,
-csrc/optim.hip), each against a plain fp64 reference of the same operation at the shapes where its code takes
+"""GPU: the decoder's non-GEMM kernels (csrc/decoder.hip, its loss in csrc/loss.hip, the fused attention pair of
+csrc/decoder_step.hip, csrc/optim.hip), each against a plain fp64 reference of the same operation at the shapes where its code takes
 another path: every arm of slab_sum, tail chunks along P, column tails along A and E, every leading stride
 different from the row length, bt = 0 / some / all rows, each optional output present and absent.
 
@@ -255,6 +255,31 @@ def test_ce_fwd_bwd(case):
     _K().ce_fwd_bwd(p["logits"], p["caps"], B, T, L, V, p["bt"], p["nrows"], outs["loss"].v, v(outs["lse"]), v(outs["dlogits"]),
                     dl_time_major=bool(tm), gscale=p["gscale"])
     DC.ce_compare(checked(outs, "ce_fwd_bwd"), DC.ce_ref(p), f"ce_fwd_bwd {DC.case_id(case)}")
+
+
+@pytest.mark.parametrize("V", [7, 257])
+def test_ce_fwd_bwd_never_follows_a_target_outside_the_vocabulary(V):
+    """Live rows (0, 0) and (1, 1) with targets V and -1: zero loss, zero lse and a zero gradient row, as
+    capmi_ce_ignore_fwd_bwd and capmi_pg_ce_fwd_bwd treat them; every other row is bit-equal to the same call
+    with valid targets in those two positions."""
+    B, T, L = DC.CE_B, DC.CE_T, DC.CE_L
+    p = dev(DC.ce_inputs((V, 1, 0, 1, 1, 1)))
+    bad = p["caps"].clone()
+    bad[0, 1], bad[1, 2] = V, -1
+    got = {}
+    for name, caps in (("valid", p["caps"]), ("outside", bad)):
+        outs = dict(loss=Out((B, T)), lse=Out((B, T)), dlogits=Out((B * T, V)))
+        _K().ce_fwd_bwd(p["logits"], caps, B, T, L, V, p["bt"], p["nrows"], outs["loss"].v, outs["lse"].v, outs["dlogits"].v,
+                        gscale=p["gscale"])
+        got[name] = checked(outs, f"ce_fwd_bwd {name} targets")
+    rows = torch.tensor([0 * T + 0, 1 * T + 1], device=DEV)
+    rest = torch.ones(B * T, dtype=torch.bool, device=DEV)
+    rest[rows] = False
+    for k, o in got["outside"].items():
+        o, ref = o.reshape(B * T, -1), got["valid"][k].reshape(B * T, -1)
+        assert bool((o[rows].view(torch.int32) == 0).all()), f"{k} of a row whose target is outside [0, V)"
+        assert bool((ref[rows] != 0).any(1).all()), f"{k}: the rows under test are live with valid targets"
+        DC.exact(o[rest], ref[rest], f"{k} of the other rows")
 
 
 @pytest.mark.parametrize("case", DC.REG_CASES, ids=DC.case_id)
