@@ -151,6 +151,8 @@ _SIGS = {
     "capmi_beam_select": [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "capmi_beam_advance": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp,
                            c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "capmi_beam_backtrack": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
+                             c_int, c_int, c_int, c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "capmi_sample_step": [c_vp, c_int, c_int, c_int, c_vp, c_float, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
                           c_vp],
     "capmi_eval_rows": [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],

@@ -224,6 +224,24 @@ class _BeamState:
             results.append((done[best][0], [], True) + extra)
         return results, last_live, paths
 
+    def finish_device(self, emit_end=False, drop=(), fallback_live=False, length_alpha=0.0):
+        """The back-trace as one launch (``capmi_beam_backtrack``), with no copy of the state to the host: per
+        image the best finished beam (score / (step + 1) ** length_alpha; the raw score at 0, as ``finish``), or
+        with ``fallback_live`` the best live beam of an image without one, as a column of the sampler's token
+        table. ``drop``: at most two token ids left out; the final END stays only with ``emit_end``. Returns device
+        tensors: tokens (T, B) int32 (-1 past a column's words), lens / finished (B,) int32, score (B,) fp32 (the
+        raw beam score), steps () int32."""
+        drop_a, drop_b = tuple(int(w) for w in drop) + (-1,) * (2 - len(drop))  # (a search checks its arguments first)
+        B, k, T, dev = self.st.B, self.st.n, self.T, self.st.dev
+        ints = torch.empty(T + 2, B, dtype=torch.int32, device=dev)
+        out = dict(tokens=ints[:T], lens=ints[T], finished=ints[T + 1],
+                   score=torch.empty(B, dtype=torch.float32, device=dev),
+                   steps=torch.full((), self.steps, dtype=torch.int32, device=dev))
+        K.beam_backtrack(self.bp, *self.fin, self.live, self.scores, self.steps, B, k, T, self.end_idx, out["tokens"],
+                         out["lens"], out["finished"], out["score"], drop_a=drop_a, drop_b=drop_b, emit_end=emit_end,
+                         fallback_live=fallback_live, length_alpha=length_alpha)
+        return out
+
 
 class BatchedBeamSearch(BeamSearch):
     """Beam search over B images per call. The beams of image i are rows i*k .. i*k+k-1 of every per-step
@@ -231,7 +249,8 @@ class BatchedBeamSearch(BeamSearch):
     and ``enc_att`` features once per image). Selection and bookkeeping are two device entry points
     (``capmi_beam_select``, ``capmi_beam_advance``), so a step needs no host sync: the host reads the device
     count of images that still have live beams every ``sync_every`` steps only, and rebuilds the sequences after
-    the loop from the back-pointers."""
+    the loop from the back-pointers. ``search_device`` leaves that walk on the device too (``capmi_beam_backtrack``)
+    and returns the captions as a token table."""
 
     def __init__(self, decoder, beam_size):
         super().__init__(decoder, beam_size)
@@ -243,14 +262,33 @@ class BatchedBeamSearch(BeamSearch):
     def _run(self, st, start_idx, end_idx, max_steps, return_all, sync_every, step_args=lambda bs, t_: ()):
         """The search on stepper ``st``; ``step_args(bs, t_)``: what its ``step`` takes at step t_ beside the
         tokens and the logits. Returns ``_BeamState.finish``'s results and paths."""
+        bs = self._loop(st, start_idx, end_idx, max_steps, sync_every, step_args)
+        results, self.last_live, paths = bs.finish(return_all)
+        self.last_stats = {"steps": bs.steps, "host_syncs": bs.syncs}
+        return results, paths
+
+    @staticmethod
+    def _loop(st, start_idx, end_idx, max_steps, sync_every, step_args):
+        """The decode steps of a search: the ``_BeamState`` they leave."""
         bs = _BeamState(st, start_idx, end_idx, max_steps, sync_every)
         for t_ in range(bs.T):
             st.step(bs.prev, bs.logits, *step_args(bs, t_))
             if bs.advance(t_):
                 break
-        results, self.last_live, paths = bs.finish(return_all)
+        return bs
+
+    def _run_device(self, st, start_idx, end_idx, max_steps, sync_every, finish_args, step_args=lambda bs, t_: ()):
+        """``_run`` with the back-trace on the device: ``_BeamState.finish_device``'s tensors."""
+        if not float(finish_args["length_alpha"]) >= 0.0:
+            raise ValueError("length_alpha must be >= 0")
+        finish_args["drop"] = tuple(finish_args["drop"])
+        if len(finish_args["drop"]) > 2:
+            raise ValueError("search_device drops at most two token ids")
+        bs = self._loop(st, start_idx, end_idx, max_steps, sync_every, step_args)
+        out = bs.finish_device(**finish_args)
+        self.last_live = None  # the live beams stay on the device
         self.last_stats = {"steps": bs.steps, "host_syncs": bs.syncs}
-        return results, paths
+        return out
 
     @torch.no_grad()
     def search(self, encoder_out, start_idx, end_idx, max_steps=50, return_all=False, return_alphas=True,
@@ -280,6 +318,19 @@ class BatchedBeamSearch(BeamSearch):
                 results[slot] = (results[slot][0], al.tolist(), True) + results[slot][3:]
         return results
 
+    @torch.no_grad()
+    def search_device(self, encoder_out, start_idx, end_idx, max_steps=50, sync_every=8, emit_end=False, drop=(),
+                      fallback_live=False, length_alpha=0.0):
+        """The launches of ``search`` without alphas, then ``_BeamState.finish_device`` (its arguments and
+        return): the captions stay on the device, as a (max_steps + 1, B) token table a ``DeviceCaptionScorer``
+        reads. ``last_stats`` counts the ``sync_every`` reads only; ``last_live`` is None."""
+        if self.dec.use_bert:
+            raise NotImplementedError("beam search with BERT features (the reference notes it fails too)")
+        st = AttentionStepper(self.dec, encoder_out, self.k)
+        return self._run_device(st, start_idx, end_idx, max_steps, sync_every,
+                                dict(emit_end=emit_end, drop=drop, fallback_live=fallback_live,
+                                     length_alpha=length_alpha), lambda bs, t_: (bs.live, None))
+
 
 class BaselineBatchedBeamSearch(BatchedBeamSearch):
     """Beam search of the baseline (LSTM) captioner over B images per call (the reference has none: the
@@ -296,3 +347,14 @@ class BaselineBatchedBeamSearch(BatchedBeamSearch):
         beams still live at the stop."""
         st = BaselineStepper(self.dec, img_features, self.k)
         return self._run(st, start_idx, end_idx, max_steps, return_all, sync_every)[0]
+
+    @torch.no_grad()
+    def search_device(self, img_features, start_idx, end_idx, max_steps=50, sync_every=8, emit_end=False, drop=(),
+                      fallback_live=False, length_alpha=0.0):
+        """``BatchedBeamSearch.search_device`` on the baseline step."""
+        if getattr(self.dec, "use_bert", False):
+            raise NotImplementedError("beam search with BERT features (the reference notes it fails too)")
+        st = BaselineStepper(self.dec, img_features, self.k)
+        return self._run_device(st, start_idx, end_idx, max_steps, sync_every,
+                                dict(emit_end=emit_end, drop=drop, fallback_live=fallback_live,
+                                     length_alpha=length_alpha))

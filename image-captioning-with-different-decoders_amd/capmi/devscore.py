@@ -5,6 +5,8 @@
                           ROUGE-L
 ``DeviceCaptionScorer``   one (T, R) token table -> per-row integers, sentence-level BLEU / ROUGE-L and CIDEr-D, all
                           device tensors (a self-critical step mixes them: capmi.scst, ``reward_mix``)
+``corpus_scores_from_rows`` the corpus formulas on per-image rows gathered from any number of ``score_table`` calls
+                          (capmi.genval scores batch by batch)
 ``caption_scores_device`` capmi.scoring.caption_scores with the counting on the device: the corpus scores of the
                           validation pass from the rows' integers, finished in fp64 with capmi.scoring's formulas
 
@@ -133,15 +135,26 @@ class DeviceCaptionScorer:
             lens[r] = len(h)
         dev = lambda a: torch.from_numpy(a).to(refs.device)  # noqa: E731
         out = self.score_table(dev(table), dev(lens), dev(np.arange(R, dtype=np.int32)))
-        stats = out["stats"].cpu().numpy().astype(np.int64)
-        cider = out["cider"].cpu().numpy().astype(np.float64)
-        s = stats[:, :REF_LEN + 1].sum(axis=0).tolist()
-        scores = {f"Bleu_{k + 1}": float(b) for k, b in enumerate(
-            bleu_from_counts(s[MATCH:MATCH + 4], s[GUESS:GUESS + 4], s[HYP_LEN], s[REF_LEN]))}
-        rows = stats[:, [LCS_P, LCS_R, LEN_R, ROUGE_HYP_LEN]].tolist()
-        scores["ROUGE_L"] = float(math.fsum(rouge_from_counts(*row) for row in rows) / R)
-        scores["CIDEr"] = float(math.fsum(cider.tolist()) / R)
-        return scores
+        return corpus_scores_from_rows(out["stats"].cpu().numpy(), out["cider"].cpu().numpy())
+
+
+def corpus_scores_from_rows(stats, cider):
+    """The six corpus scores from the rows ``score_table`` gives, one row per image: ``stats`` (N,
+    CAPMI_SCORE_STATS) integers, ``cider`` (N,) floats, on the host. BLEU from the ten summed integers and ROUGE-L
+    from the rows' integers in fp64, CIDEr the fp64 mean of the rows' rewards. A pass that scores batch by batch
+    gathers its rows into one table and calls this once."""
+    stats = np.asarray(stats).astype(np.int64)
+    cider = np.asarray(cider).astype(np.float64)
+    R = stats.shape[0]
+    if stats.ndim != 2 or stats.shape[1] != CAPMI_SCORE_STATS or cider.shape != (R,) or R < 1:
+        raise ValueError("corpus_scores_from_rows takes (N, CAPMI_SCORE_STATS) integers and (N,) floats, N >= 1")
+    s = stats[:, :REF_LEN + 1].sum(axis=0).tolist()
+    scores = {f"Bleu_{k + 1}": float(b) for k, b in enumerate(
+        bleu_from_counts(s[MATCH:MATCH + 4], s[GUESS:GUESS + 4], s[HYP_LEN], s[REF_LEN]))}
+    rows = stats[:, [LCS_P, LCS_R, LEN_R, ROUGE_HYP_LEN]].tolist()
+    scores["ROUGE_L"] = float(math.fsum(rouge_from_counts(*row) for row in rows) / R)
+    scores["CIDEr"] = float(math.fsum(cider.tolist()) / R)
+    return scores
 
 
 def bleu_from_counts(correct, guess, hyp_len, ref_len):

@@ -720,6 +720,26 @@ def beam_advance(parent, word, top, live, B, k, D, end_idx, step, h_src, c_src, 
          ptr(bp_src), ptr(fin_count), ptr(fin_step), ptr(fin_slot), ptr(fin_score), ptr(images_live), stream())
 
 
+def beam_backtrack(bp, fin_count, fin_step, fin_slot, fin_score, live, scores, steps, B, k, T, end_idx, tokens, lens,
+                   finished, score, alpha_rows=None, drop_a=-1, drop_b=-1, emit_end=False, fallback_live=False,
+                   length_alpha=0.0):
+    """bp (T, 3, B*k) and the finished lists as ``beam_advance`` leaves them after ``steps`` steps -> tokens (T, B)
+    int32, lens / finished (B,) int32, score (B,) fp32, alpha_rows (T, B) int32 or None. See capmi_beam_backtrack in
+    capmi.h."""
+    _cuda(fin_score, scores, score)
+    _cuda(bp, fin_count, fin_step, fin_slot, live, tokens, lens, finished, alpha_rows, dtype=torch.int32)
+    n = B * k
+    assert bp.is_contiguous() and bp.numel() >= T * 3 * n and min(fin_count.numel(), live.numel()) >= B
+    assert min(x.numel() for x in (fin_step, fin_slot, fin_score, scores)) >= n
+    assert tokens.is_contiguous() and tokens.numel() >= T * B
+    assert min(lens.numel(), finished.numel(), score.numel()) >= B
+    assert alpha_rows is None or (alpha_rows.is_contiguous() and alpha_rows.numel() >= T * B)
+    call("capmi_beam_backtrack", ptr(bp), ptr(fin_count), ptr(fin_step), ptr(fin_slot), ptr(fin_score), ptr(live),
+         ptr(scores), int(steps), B, k, T, int(end_idx), int(drop_a), int(drop_b), int(bool(emit_end)),
+         int(bool(fallback_live)), float(length_alpha), ptr(tokens), ptr(lens), ptr(finished), ptr(score),
+         ptr(alpha_rows), stream())
+
+
 # --------------------------------------------------------------------------------------
 # sampled decoding (csrc/sample.hip): one launch draws the next token of every alive row
 # --------------------------------------------------------------------------------------

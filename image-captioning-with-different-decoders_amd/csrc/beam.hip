@@ -12,6 +12,8 @@
 //                        arg-max), then the per-image merge of those <= k*s candidates by rank counting
 //   capmi_beam_advance : one launch: finished beams recorded, survivors compacted, h/c gathered from
 //                        their parents, next words / scores / back-pointers / live counts written
+//   capmi_beam_backtrack : after the loop, one launch: per image the best finished beam walked back through
+//                        the back-pointers into the sampler's (T, B) token table, so the scorer reads it in place
 #include <limits.h>
 
 #include "common.h"
@@ -435,6 +437,125 @@ extern "C" int capmi_beam_advance(const int* parent, const int* word, const floa
   hipLaunchKernelGGL(beam_advance_kernel, dim3(B), dim3(256), 0, as_stream(stream), parent, word, top, live, k, D,
                      end_idx, step, h_src, c_src, h_dst, c_dst, prev, scores, bp_parent, bp_word, bp_src, fin_count,
                      fin_step, fin_slot, fin_score, images_live);
+  CAPMI_LAUNCH_CHECK();
+  return 0;
+}
+
+// --------------------------------------------------------------------------------------
+// back-trace after the loop, one thread per image: the finished beam with the largest key (or, with
+// fallback_live, live row 0 at the last step) is walked back through the back-pointers twice, once to count
+// the words it keeps and once to write them from position 0 of column i of the (T, B) token table. Every
+// index read from the state (finished count, step, slot, parent row) is checked against its range during
+// the first walk; a path that leaves it gives length 0, so the second walk reads only what the first saw.
+// --------------------------------------------------------------------------------------
+constexpr int BEAM_BT_T = 64;
+
+__global__ void __launch_bounds__(BEAM_BT_T) beam_backtrack_kernel(
+    const int* __restrict__ bp, const int* __restrict__ fin_count, const int* __restrict__ fin_step,
+    const int* __restrict__ fin_slot, const float* __restrict__ fin_score, const int* __restrict__ live,
+    const float* __restrict__ scores, int steps, int B, int k, int T, int end_idx, int drop_a, int drop_b,
+    int emit_end, int fallback_live, double length_alpha, int* __restrict__ tokens, int* __restrict__ lens,
+    int* __restrict__ finished, float* __restrict__ score, int* __restrict__ alpha_rows) {
+  const int i = blockIdx.x * BEAM_BT_T + threadIdx.x;
+  if (i >= B) return;
+  const long long R = (long long)B * k, row0 = (long long)i * k;
+  const int* bp_i = bp + row0;  // bp[t][c][i*k + s] = bp_i[(t*3 + c)*R + s]
+  int t0 = -1, s0 = 0, fin = 0;
+  float sc = 0.f;
+  const int nf = min(fin_count[i], k);
+  if (nf > 0) {
+    int best = 0;
+    if (length_alpha == 0.0) {
+      float bv = fin_score[row0];
+      for (int q = 1; q < nf; ++q) {
+        const float v = fin_score[row0 + q];
+        if (v > bv) {
+          bv = v;
+          best = q;
+        }
+      }
+    } else {
+      double bv = (double)fin_score[row0] / pow((double)fin_step[row0] + 1.0, length_alpha);
+      for (int q = 1; q < nf; ++q) {
+        const double v = (double)fin_score[row0 + q] / pow((double)fin_step[row0 + q] + 1.0, length_alpha);
+        if (v > bv) {
+          bv = v;
+          best = q;
+        }
+      }
+    }
+    t0 = fin_step[row0 + best];
+    s0 = fin_slot[row0 + best];
+    sc = fin_score[row0 + best];
+    fin = 1;
+  } else if (fallback_live && live[i] > 0 && steps > 0) {
+    t0 = steps - 1;
+    s0 = bp_i[((long long)t0 * 3 + 2) * R];
+    sc = scores[row0];
+  }
+  bool ok = t0 >= 0 && t0 < steps && s0 >= 0 && s0 < k;
+  const int t_end = t0;  // the step whose END is the sequence's last word
+  const auto kept = [&](int t, int w) {
+    return w != drop_a && w != drop_b && !(t == t_end && w == end_idx && !emit_end);
+  };
+  int n = 0;
+  if (ok) {
+    int t = t0, s = s0;
+    while (true) {
+      const int row = bp_i[((long long)t * 3 + 0) * R + s], w = bp_i[((long long)t * 3 + 1) * R + s];
+      if (row < 0 || row >= k) {
+        ok = false;
+        break;
+      }
+      n += kept(t, w) ? 1 : 0;
+      if (t == 0) break;
+      --t;
+      s = bp_i[((long long)t * 3 + 2) * R + row];
+      if (s < 0 || s >= k) {
+        ok = false;
+        break;
+      }
+    }
+  }
+  if (!ok) {
+    n = 0;
+    t0 = -1;
+    fin = 0;
+    sc = 0.f;
+  }
+  lens[i] = n;
+  finished[i] = fin;
+  score[i] = sc;
+  for (int t = n; t < T; ++t) tokens[(long long)t * B + i] = -1;
+  if (alpha_rows)
+    for (int t = t0 + 1; t < T; ++t) alpha_rows[(long long)t * B + i] = -1;
+  if (!ok) return;
+  int t = t0, s = s0, pos = n;
+  while (true) {
+    const int row = bp_i[((long long)t * 3 + 0) * R + s], w = bp_i[((long long)t * 3 + 1) * R + s];
+    if (kept(t, w)) tokens[(long long)(--pos) * B + i] = w;
+    if (alpha_rows) alpha_rows[(long long)t * B + i] = (int)((long long)t * R + row0 + row);
+    if (t == 0) break;
+    --t;
+    s = bp_i[((long long)t * 3 + 2) * R + row];
+  }
+}
+
+extern "C" int capmi_beam_backtrack(const int* bp, const int* fin_count, const int* fin_step, const int* fin_slot,
+                                    const float* fin_score, const int* live, const float* scores, int steps, int B,
+                                    int k, int T, int end_idx, int drop_a, int drop_b, int emit_end,
+                                    int fallback_live, double length_alpha, int* tokens, int* lens, int* finished,
+                                    float* score, int* alpha_rows, void* stream) {
+  CAPMI_REQUIRE(bp && fin_count && fin_step && fin_slot && fin_score && live && scores, CAPMI_EINVAL);
+  CAPMI_REQUIRE(tokens && lens && finished && score, CAPMI_EINVAL);
+  CAPMI_REQUIRE(B >= 1 && k >= 1 && k <= BEAM_KMAX && T >= 1 && steps >= 0 && steps <= T && end_idx >= 0,
+                CAPMI_EINVAL);
+  CAPMI_REQUIRE(length_alpha >= 0.0, CAPMI_EINVAL);  // a NaN fails the comparison too
+  // T * R * 3 < 2^31 (the first test keeps the product inside 64 bits)
+  CAPMI_REQUIRE((long long)B * k * 3 < (1LL << 31) && (long long)T * B * k * 3 < (1LL << 31), CAPMI_ERANGE);
+  hipLaunchKernelGGL(beam_backtrack_kernel, dim3(cdiv(B, BEAM_BT_T)), dim3(BEAM_BT_T), 0, as_stream(stream), bp,
+                     fin_count, fin_step, fin_slot, fin_score, live, scores, steps, B, k, T, end_idx, drop_a, drop_b,
+                     emit_end, fallback_live, length_alpha, tokens, lens, finished, score, alpha_rows);
   CAPMI_LAUNCH_CHECK();
   return 0;
 }

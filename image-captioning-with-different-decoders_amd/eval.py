@@ -3,6 +3,7 @@
     python eval.py basic_att_0.pth.tar --model_type attention [--batch_size 64]
     python eval.py basic_att_0.pth.tar --model_type attention --batch_size 64 --synthetic_size 512
     python eval.py baseline_0.pth.tar --model_type baseline --batch_size 64 --synthetic_size 512
+    python eval.py basic_att_0.pth.tar --model_type attention --batch_size 64 --decode beam --beam_size 3
 
 The reference's arguments are kept: ``checkpoint`` (a file in ./checkpoints), ``--model_type``,
 ``--max_caption_length``, ``--print_freq``. Added: ``--batch_size`` (1, the default, runs the reference's
@@ -10,7 +11,10 @@ one-caption-at-a-time ``evaluate``; larger runs ``evaluate_batched`` of models.a
 whose per-caption numbers are the same),``--synthetic_size`` / ``--vocab_size`` / ``--synthetic_len`` (COCO-shaped synthetic
 captions of ragged lengths instead of the COCO 'val' set), ``--scorer device`` (the batched pass counts BLEU /
 ROUGE-L / CIDEr on the HIP device, capmi.devscore; ``host``, the default, is capmi.scoring) and
-``--trusted_checkpoint`` (as train.py: the reference's whole-module checkpoints are pickles). The metrics are
+``--trusted_checkpoint`` (as train.py: the reference's whole-module checkpoints are pickles). ``--decode beam``
+(with ``--beam_size``, ``--max_decode_len``, ``--length_alpha``) replaces the teacher-forced pass by validation on
+generated captions (capmi.genval): every image captioned once by beam search and scored against all of its references
+on the HIP device, for either ``--model_type``. The metrics are
 printed and written to <PathConfig.eval_data>/<checkpoint stem>.json.
 """
 import argparse
@@ -52,6 +56,15 @@ def parse_args(argv=None):
     parser.add_argument('--scorer', type=str, default='host', choices=['host', 'device'],
                         help='where the batched pass scores its captions: capmi.scoring on the host or '
                              'capmi.devscore on the HIP device.')
+    parser.add_argument('--decode', type=str, default='teacher', choices=['teacher', 'beam'],
+                        help='teacher: the teacher-forced pass. beam: every image captioned once by beam search and '
+                             'scored against all of its references on the HIP device (capmi.genval).')
+    parser.add_argument('--beam_size', type=int, default=3, help='beams per image of --decode beam.')
+    parser.add_argument('--max_decode_len', type=int, default=50,
+                        help='longest caption of --decode beam, in words (at most 63).')
+    parser.add_argument('--length_alpha', type=float, default=0.0,
+                        help='--decode beam picks the finished beam with the largest score / length^alpha '
+                             '(0: the raw score, as gen_captions.py).')
     args = parser.parse_args(argv)
     if args.batch_size < 1:
         parser.error('--batch_size must be >= 1')
@@ -122,7 +135,11 @@ def main(argv=None):
             encoder, decoder = _baseline_models(args, encoder, decoder, device)
         else:
             encoder, decoder = encoder.to(device), decoder.to(device)
-        metrics = evaluate_baseline_model(device, args, encoder, decoder)
+        if args.decode == 'beam':
+            from models.baseline import evaluate_generated
+            metrics = evaluate_generated(device, args, encoder, decoder, batch_size=args.batch_size)
+        else:
+            metrics = evaluate_baseline_model(device, args, encoder, decoder)
     elif args.model_type == 'attention':
         from models.attention import evaluate as evaluate_attention_model, evaluate_batched
         dataset = _synthetic_dataset(args) if args.synthetic_size > 0 else None
@@ -137,13 +154,16 @@ def main(argv=None):
             encoder, decoder = _attention_models(args, encoder, decoder, vocab, device)
         else:
             encoder, decoder = encoder.to(device), decoder.to(device)
-        if args.batch_size > 1:
+        if args.decode == 'beam':
+            from models.attention import evaluate_generated
+            metrics = evaluate_generated(device, args, encoder, decoder, dataset=dataset, batch_size=args.batch_size)
+        elif args.batch_size > 1:
             metrics = evaluate_batched(device, args, encoder, decoder, dataset=dataset, batch_size=args.batch_size)
         else:
             metrics = evaluate_attention_model(device, args, encoder, decoder, val_loader=_loader_1(dataset, decoder))
     else:
         raise SystemExit('--model_type must be baseline or attention')
-    print({k: v for k, v in metrics.items() if k not in ('references', 'hypotheses', 'losses')})
+    print({k: v for k, v in metrics.items() if k not in ('references', 'hypotheses', 'losses', 'image_keys')})
     path = save_eval_data(name, metrics)
     print(f'Saved evaluation data to {path}')
     return metrics

@@ -501,5 +501,28 @@ def evaluate_batched(device, args, encoder, decoder, dataset=None, batch_size=64
     return metrics
 
 
+def evaluate_generated(device, args, encoder, decoder, dataset=None, batch_size=64):
+    """Validation on generated captions (capmi.genval): every image of ``dataset`` (default the COCO 'val' set) is
+    captioned once by ``BatchedBeamSearch`` with ``args.beam_size`` beams (default 3), at most
+    ``args.max_decode_len`` words (default 50, at most 63) and the length normalisation ``args.length_alpha``
+    (default 0: the raw beam score), and scored against all of its references. Captions, counting and CIDEr-D
+    rows stay on the device; the host synchronises every ``print_freq`` batches and at the end.
+
+    Returns a JSON-serialisable dict: the capmi.scoring.caption_scores keys, ``hypotheses`` (token ids per image,
+    in image order, START / END / PAD stripped), ``image_keys``, ``unfinished`` (images without a finished beam:
+    their best live beam is scored), ``mean_length``, ``host_syncs`` (the searches' ``sync_every`` reads) and
+    ``captions_per_s`` (over everything from the reference tables' build to the scores). ``max_decode_len`` above 63
+    is a ``ValueError``."""
+    from capmi import genval
+    from capmi.beam import BatchedBeamSearch
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("generated-caption validation runs on a HIP device (the search and the scores are kernels)")
+    if dataset is None:
+        from dataset import COCODataset  # real COCO path (pycocotools, nltk, images)
+        dataset = COCODataset(mode='val', caption_max_len=getattr(args, "max_caption_length", -1))
+    search = BatchedBeamSearch(decoder, int(getattr(args, "beam_size", 3)))
+    return genval.evaluate_generated(device, args, encoder, decoder, search, dataset, decoder.vocab, batch_size)
+
+
 __all__ = ["SoftAttention", "AttentionDecoderParams", "AttentionDecoder", "train", "train_self_critical", "evaluate",
-           "evaluate_batched"]
+           "evaluate_batched", "evaluate_generated"]

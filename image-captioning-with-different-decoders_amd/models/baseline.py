@@ -573,3 +573,18 @@ def evaluate_batched(device, args, encoder, decoder, dataset=None, batch_size=64
     print(f'Checkpoint {getattr(args, "checkpoint", None)} finished evaluation in '
           f'{time.time() - start_time:.4f} seconds.')
     return metrics
+
+
+def evaluate_generated(device, args, encoder, decoder, dataset=None, batch_size=64):
+    """Validation on generated captions (capmi.genval), as models.attention.evaluate_generated: every image of
+    ``dataset`` (default: ``_eval_dataset(args)``) captioned once by ``BaselineBatchedBeamSearch`` and scored against
+    all of its references on the device. The vocabulary is the dataset's. Same arguments read off ``args``
+    (``beam_size``, ``max_decode_len``, ``length_alpha``, ``print_freq``), same returned keys."""
+    from capmi import genval
+    from capmi.beam import BaselineBatchedBeamSearch
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("generated-caption validation runs on a HIP device (the search and the scores are kernels)")
+    if dataset is None:
+        dataset = _eval_dataset(args)
+    search = BaselineBatchedBeamSearch(decoder, int(getattr(args, "beam_size", 3)))
+    return genval.evaluate_generated(device, args, encoder, decoder, search, dataset, dataset.vocab, batch_size)

@@ -588,6 +588,29 @@ int capmi_beam_advance(const int* parent, const int* word, const float* top, int
                        float* h_dst, float* c_dst, long long* prev, float* scores, int* bp_parent,
                        int* bp_word, int* bp_src, int* fin_count, int* fin_step, int* fin_slot,
                        float* fin_score, int* images_live, void* stream);
+/* The sequences after the loop, in the sampler's token-table layout (what capmi_cider_reward and
+ * capmi_caption_stats read). New symbol only, added without an ABI bump (purely additive). Inputs as
+ * capmi_beam_advance leaves them after `steps` steps (0..T): bp [T][3][B*k] (slice 0 the parent row by slot,
+ * 1 the word by slot, 2 the source slot by new row), the finished lists, live [B], scores [B*k].
+ * Per image with fin_count > 0: the finished beam with the largest key, the first on a tie; the key is
+ * fin_score compared as fp32 when length_alpha == 0, else (double)fin_score / pow(fin_step + 1, length_alpha)
+ * in fp64. With fin_count == 0: live row 0 at step steps-1 (the best live beam: selection order is descending
+ * and compaction keeps it) when fallback_live, live[i] > 0 and steps > 0; otherwise nothing.
+ * The beam selected at step t as slot s took word bp[t][1][s] from row bp[t][0][s], which was selected at
+ * step t-1 as slot bp[t-1][2][row]. Outputs: tokens [T][B] int32, column i = the kept words from position 0,
+ * then -1 (every entry is written): a word equal to drop_a or drop_b (-1: none) is left out, and the last
+ * step's END (end_idx) is kept only with emit_end. lens [B] = the number of kept words, finished [B] = 0/1,
+ * score [B] = the raw fin_score or live score (0 when nothing is emitted). alpha_rows [T][B] (optional):
+ * for every step t of the path, dropped words and the END step included, the row t*B*k + i*k + row of a
+ * [T*B*k][P] alpha table; -1 past the path. Any count, step, slot or row of the state outside its range
+ * gives that image length 0, finished 0, score 0: nothing is read out of bounds.
+ * CAPMI_EINVAL: a NULL required pointer, B < 1, k outside 1..16, T < 1, steps outside 0..T, end_idx < 0, a
+ * NaN or negative length_alpha. CAPMI_ERANGE: T*B*k*3 >= 2^31. */
+int capmi_beam_backtrack(const int* bp, const int* fin_count, const int* fin_step, const int* fin_slot,
+                         const float* fin_score, const int* live, const float* scores, int steps, int B,
+                         int k, int T, int end_idx, int drop_a, int drop_b, int emit_end, int fallback_live,
+                         double length_alpha, int* tokens, int* lens, int* finished, float* score,
+                         int* alpha_rows, void* stream);
 
 /* ------------------------------------------------------------------------
  * Sampled decoding (csrc/sample.hip). New symbol only, nothing existing changed; added without an ABI bump
